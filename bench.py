@@ -28,6 +28,14 @@ Modes
                    --scaling weak and N > 1 the same leg is measured after the row-sharded figure (`replicated` object).
   --workload cfg3  (BASELINE.json configs[2]) synthetic 100 000 codes x 512-d, 1 000 queries, per-code min + argmin.
 
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, ...).  Everything
+else the script measures or checks - roofline and per-kernel figures, the eager leg behind graph replays, the f64 line,
+clips in flight, the mixed-precision comparison with the f64 sweep, the VQ-VAE, cold, end-to-end and CPU-baseline legs,
+the sub-records of the other BASELINE configurations - runs only with --full.
+--dump-outputs DIR writes what the timed path returned in its last step (the matched codes; the encoded ids with
+--encode-batch; cfg3: the per-code tables) as DIR/<name>.npy in float64.  The inputs are seeded: the same arguments give
+the same inputs in every run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -55,19 +63,22 @@ DATA = "gaussian"      # --data: "gaussian" (i.i.d. N(0,1): SURVEY.md §8d) or "
 
 def chunked_db(n_db, lo, hi, seed, F=1024):
     """Rows [lo,hi) of the synthetic DB, generated in 64-window chunks with per-chunk seeds so that
-    every rank can build just its shard (and the CPU baseline just its sample)."""
+    every rank can build just its shard (and the CPU baseline just its sample).  The gaussian chunks are generated on a few
+    host threads (NumPy's generators and torch release the GIL); each has its own seed, so the bytes do not depend on it.
+    (The speech-like transform goes through a BLAS product: one thread, as it always ran.)"""
+    from concurrent.futures import ThreadPoolExecutor
     from qpgesture_amd import synth
     from qpgesture_amd.data_processing import interp_wavlm
-    parts = []
-    c0 = (lo // 64) * 64
-    while c0 < hi:
+
+    def chunk(c0):
         n = min(64, n_db - c0)
         d = synth.make_db(n, seed * 100003 + c0 // 64, F)
         if DATA == "speechlike":
             synth.speechlike_transform(d, 5000011 + seed * 100003 + c0 // 64)
         a, b = max(lo, c0) - c0, min(hi, c0 + n) - c0
-        parts.append(dict(interp=interp_wavlm(d["wavlm"][a:b]), ctx=d["context"][a:b].squeeze(2)))
-        c0 += 64
+        return dict(interp=interp_wavlm(d["wavlm"][a:b]), ctx=d["context"][a:b].squeeze(2))
+    with ThreadPoolExecutor(1 if DATA == "speechlike" else min(16, len(os.sched_getaffinity(0)))) as ex:
+        parts = list(ex.map(chunk, range((lo // 64) * 64, hi, 64)))
     return (np.concatenate([p["interp"] for p in parts]), np.concatenate([p["ctx"] for p in parts]))
 
 
@@ -94,6 +105,11 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline figure (roofline, eager leg, f64 line, "
+                         "pipelined, mixed-precision comparison, VQ-VAE, cold, end-to-end, CPU baseline, sub-records)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--n-db", type=int, default=None, help="DB windows (default 2048; 8192 with --scaling strong)")
     ap.add_argument("--windows", type=int, default=6)
     ap.add_argument("--scaling", choices=["weak", "strong", "replicated"], default="weak")
@@ -223,7 +239,10 @@ def main():
         lib_coll, lib_coll_why = _par.negotiate_lib_collectives(dev)      # (every rank ends up on the same transport)
 
     if a.workload == "cfg3":
-        out = cfg3_bench(a, dev, world, rank)
+        outputs = {} if a.dump_outputs else None
+        out = cfg3_bench(a, dev, world, rank, outputs)
+        if outputs is not None:
+            dump_outputs(a.dump_outputs, outputs, world, rank)
         if rank == 0:
             print(json.dumps(out), file=JSON_OUT, flush=True)
         if world > 1 or force_sharded:
@@ -296,12 +315,15 @@ def main():
         te_ctx = te_ctx[rank * CL * M:(rank + 1) * CL * M].contiguous()
     n_sweep_clips = CL if replicated else n_clips
 
+    last_ids = [None]                   # (--dump-outputs: the encode leg's ids of the last step)
+
     def step_eager():
         # weak, N > 1: every rank sweeps all clips' queries against its DB shard; ONE all-to-all leaves each rank with
         # the final tables of its own clips.  strong: ONE all-gather + merge, every rank holds the clip's tables.
         # replicated: this rank's clips against the whole DB, no exchange.
         if enc is not None:
             ids = enc.encode_f16x3(enc_x) if a.encode_precision == "f16x3" else enc.encode(enc_x)[0]
+            last_ids[0] = ids
         T = knn.sweep_tables(te_interp, te_ctx, M * n_sweep_clips, owner_blocks=sharded_run and not strong, for_walk=True)
         if my_clips > 1 and batch_walk:
             # the clips are independent chains (their own seeds / window chaining): ONE set of walk launches for all
@@ -425,7 +447,7 @@ def main():
         else:
             arr, cgx = cg.run_ints(seed_code, seed_phase), cg
         if enc is not None:
-            cg.encoded_ids(arr)                    # (f16x3: windows the margin check flagged are re-encoded in f32 HERE)
+            last_ids[0] = cg.encoded_ids(arr)      # (f16x3: windows the margin check flagged are re-encoded in f32 HERE)
         st_ = cgx.statuses(arr)
         if (st_[:, 1] != 0).any():                 # a trouble word came out with the codes: this step again, eagerly
             graph_fallbacks[0] += 1                # (ClipGraph.wait_ints cleared the capture's matcher's sticky word)
@@ -543,6 +565,11 @@ def main():
     dt = time.perf_counter() - t0
     cut_used = bool(getattr(knn_g if graph_mode else knn, "_last_rank_cut", False))     # (of the timed steps' last sweep)
     gc.enable()
+    if a.dump_outputs:
+        dumped = {"codes": codes.numpy()}
+        if last_ids[0] is not None:
+            dumped["encoded_ids"] = last_ids[0].cpu().numpy() if torch.is_tensor(last_ids[0]) else last_ids[0]
+        dump_outputs(a.dump_outputs, dumped, world, rank)
     if os.environ.get("QPG_BENCH_STEP_TIMES", "") == "1" and pipe is None:
         print("per-step ms (timed region):", ["%.3f" % (x * 1e3) for x in step_times[-a.steps:]], file=sys.stderr)
     if prof is not None:
@@ -554,7 +581,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     eager_leg = None
-    if graph_mode:
+    if graph_mode and a.full:
         # the eager figure and the sweep kernel's HIP-event timing: the same K steps, one launch per kernel, right behind
         # the timed region (events cannot bracket a node of a replayed graph); the pool of events exists already
         for _ in range(max(a.warmup, 10)):
@@ -589,7 +616,7 @@ def main():
     value = frames_per_step * a.steps / dt
 
     serial = None
-    if pipe is not None:
+    if pipe is not None and a.full:
         # the same clip, one at a time (a step = submit + wait): the latency figure, and the sweep kernel alone on the GPU
         n1 = min(a.steps, 100)
         for _ in range(10):
@@ -625,8 +652,11 @@ def main():
     alg_bytes = db.n_local * 81 * db.F * fb + C * 8 + Q * 6 * db.F * 4 + Q * C * 8
     default_shape = world == 1 and N == 2048 and M == 6 and CL == 1 and fb == 4
     peak = F32_MFMA_PEAK_TFLOPS if mixed else F64_MFMA_PEAK_TFLOPS
-    hl = bool(mixed and getattr(knn, "_last_audio_hl", False))
-    if hl:
+    timed_knn = knn_g if graph_mode else (pipe.lanes[0]["knn"] if pipe is not None else knn)
+    hl = bool(mixed and getattr(timed_knn, "_last_audio_hl", False))
+    if not a.full:
+        roofline = None                  # (the dominant kernel's figures: --full)
+    elif hl:
         # split-operand f16 sweep: every database frame is read once from the frame-major image (27 super-rows x 3 frames
         # x F x 4 B per window = the 81 even frames), the matrix leaves in f32; three f16 MFMAs per 32 k-steps of a
         # 32-row x 96-column tile (27 of 32 rows live)
@@ -730,9 +760,11 @@ def main():
            "roofline": roofline,
            "realtime_factor": round(24.0 * M / 6 / (dt / a.steps), 1) if strong
            else round(value / 60.0 / world, 1)}
+    if roofline is None:
+        del out["roofline"]
 
     out["data"] = "synthetic" if a.data == "gaussian" else "synthetic, speech-like statistics (synth.speechlike_transform)"
-    if mixed and not sharded_run and pipe is None:
+    if a.full and mixed and not sharded_run and pipe is None:
         ln = knn.tier1_list_lengths()
         if ln.size:
             out["band_lists"] = {"tier1_entries_per_query": {"min": int(ln.min()), "median": int(np.median(ln)),
@@ -743,7 +775,7 @@ def main():
     out["rematched_steps"] = rematched[0] + (pipe.fallbacks if pipe is not None else 0)
     if world > 1 or force_sharded:
         out["ranks_seen"] = ranks_seen(dev, world, rank, one_gpu == "1")
-    if mixed and not sharded_run and world == 1 and CL == 1 and pipe is None and enc is None and not a.no_f64_line:
+    if a.full and mixed and not sharded_run and world == 1 and CL == 1 and pipe is None and enc is None and not a.no_f64_line:
         # the reference-precision figure beside the mixed one, in the same record: 20 more steps with the f64 sweep
         knn.audio_precision = "f64"
         pool6 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(28)]
@@ -782,7 +814,7 @@ def main():
                               **({"library_transport_unavailable": lib_coll_why} if lib_coll_why else {})}
     if graph_fallback:
         out["step_mode_fallback"] = graph_fallback
-    if graph_mode:
+    if graph_mode and a.full:
         out["eager"] = eager_leg
         # another seed through the SAME capture must equal the eager path started from that seed
         sc2 = (seed_code + 101) % 512
@@ -815,7 +847,7 @@ def main():
                                "text_side_captured_first": bool(not knn_g.audio_first and knn_g.audio_first is not None),
                                "other_seed_equals_eager": same2,
                                **({"segments": list(cg.segment_kinds)} if cg.segmented else {})}
-    if (mixed and not sharded_run and world == 1 and can_pipe and pipe is None and not a.no_f64_line and
+    if (a.full and mixed and not sharded_run and world == 1 and can_pipe and pipe is None and not a.no_f64_line and
             os.environ.get("QPG_BENCH_NO_PIPELINED", "") != "1"):
         # Clips in flight (round 6: GraphPipeline).  Round 5's figure here came from ClipPipeline's eager lanes: host-bound
         # (~0.25 ms of Python per clip) and without overlap - a one-chunk sweep holds every register of every CU, so another
@@ -898,14 +930,14 @@ def main():
         serial["roofline_frac"] = (round(alg_bytes / (serial["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if hl else
                                    round(flops / (serial["kernel_ms"] * 1e-3) / 1e12 / peak, 4))
         out["one_clip_at_a_time"] = serial
-    if mixed and sharded_run:
+    if a.full and mixed and sharded_run:
         st = knn.mixed_stats()
         fl = knn._guard_stats.cpu().numpy()
         n_run = a.steps + a.warmup + prewarm["steps"]
         out["mixed_precision"] = {"shard_f64_dot_pairs_per_step": round(st["tier1_pairs"] / n_run, 1),
                                   "cross_shard_reevaluations_per_step": round(int(fl[3]) / n_run, 1),
                                   "flags": st["flags"], "error_bound": 1.3e-6 if hl else 2.05e-6}
-    if mixed and not sharded_run:
+    if a.full and mixed and not sharded_run:
         # re-evaluation activity of the timed steps (+ warm-up) and the same clip through the f64 sweep: the mixed path
         # must return the same codes (its tables differ only inside the sweep's error bound)
         st = knn.mixed_stats()
@@ -948,16 +980,16 @@ def main():
             "winners_equal_f64_sweep": bool(torch.equal(Tm["aud_idx"], T64["aud_idx"])),
             "ranks_equal_f64_sweep": bool(torch.equal(Tm["aud_rank"], T64["aud_rank"])),
             "codes_equal_f64_sweep": same}
-    if world > 1 and not replicated and not strong and not a.no_replicated and not force_sharded and CL == 1:
+    if a.full and world > 1 and not replicated and not strong and not a.no_replicated and not force_sharded and CL == 1:
         out["replicated"] = replicated_leg(a, dev, world, rank, N, M, code, phase, sig, te_interp_all, te_ctx_all,
                                            seed_code, seed_phase_d, codes if a.check else None)
-    if not a.no_vqvae:
+    if a.full and not a.no_vqvae:
         out.update(vqvae_bench(dev, a, world, rank))
-    if rank == 0 and world == 1 and CL == 1 and not a.no_cold and fb == 4:
+    if a.full and rank == 0 and world == 1 and CL == 1 and not a.no_cold and fb == 4:
         out["cold"] = cold_bench(dev, N, M)
-    if rank == 0 and world == 1 and CL == 1 and not a.no_e2e and not a.no_cold and fb == 4 and a.data == "gaussian":
+    if a.full and rank == 0 and world == 1 and CL == 1 and not a.no_e2e and not a.no_cold and fb == 4 and a.data == "gaussian":
         out["e2e_cli"] = e2e_cli_bench(dev, N, M)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and fb == 4:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and fb == 4:
         out["cpu_baseline"] = cpu_baseline(a, code, clips[0], M, N)
         out["vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
     if a.check:
@@ -975,8 +1007,9 @@ def main():
         ok = bool(np.array_equal(np.concatenate(want), codes.numpy().astype(np.int64)))
         out["check"] = ok
         assert ok, "rank %d: sharded result differs from the single-rank result" % rank
-    if (rank == 0 and world == 1 and default_shape and a.workload == "match" and a.data == "gaussian" and not force_sharded
-            and a.clips_in_flight == 1 and not a.encode_batch and not a.no_sub_records and a.audio_precision == "mixed"):
+    if (a.full and rank == 0 and world == 1 and default_shape and a.workload == "match" and a.data == "gaussian"
+            and not force_sharded and a.clips_in_flight == 1 and not a.encode_batch and not a.no_sub_records
+            and a.audio_precision == "mixed"):
         out["sub_records"] = sub_records(dev)
     if rank == 0:
         print(json.dumps(out), file=JSON_OUT, flush=True)
@@ -1001,7 +1034,8 @@ SUB_RUNS = [
      ["--clips", "16", "--feature-dtype", "f16", "--encode-batch", "96", "--encode-precision", "f16x3", "--steps", "20",
       "--warmup", "3"]),
 ]
-SUB_COMMON = ["--gpus", "1", "--no-sub-records", "--no-cpu-baseline", "--no-vqvae", "--no-cold", "--no-e2e", "--no-f64-line"]
+SUB_COMMON = ["--gpus", "1", "--full", "--no-sub-records", "--no-cpu-baseline", "--no-vqvae", "--no-cold", "--no-e2e",
+              "--no-f64-line"]
 
 
 def sub_records(dev):
@@ -1412,14 +1446,29 @@ def cold_bench(dev, N, M):
                     "WavLM + context in, (M,30) codes out"}
 
 
-def cfg3_bench(a, dev, world, rank):
+def cfg3_bench(a, dev, world, rank, outputs=None):
     """BASELINE.json configs[2] / SURVEY §8d cfg-3: DB X f32 (100 000, 512) ~N(0,1) seed 0, code ids uniform [0,512)
     seed 1, validity mask Bernoulli(0.9) seed 2, queries (1000, 512) seed 3; per (query, code) min cosine distance +
     argmin.  Runs the exact-f32 (sklearn-order) sweep with the per-code min fused into its epilogue: the Q x C
     distance matrix never reaches HBM."""
     import torch
     from qpgesture_amd import cfg3
-    return cfg3.bench(a, dev, world, rank, HBM_PEAK_GBS)
+    return cfg3.bench(a, dev, world, rank, HBM_PEAK_GBS, outputs=outputs)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, world, rank):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (integer results are exact in it); with N > 1 ranks each
+    rank writes its own, <name>_rank<r>.npy.  At most DUMP_LIMIT_BYTES in all."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in conv.values()) * world
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for k, v in conv.items():
+        np.save(os.path.join(path, (k + "_rank%d" % rank if world > 1 else k) + ".npy"), v)
 
 
 class _ShardView:

@@ -28,7 +28,7 @@ def test_bench_sharded_matches_unsharded(world):
     env = dict(os.environ, QPG_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--n-db", "200", "--windows", "2", "--check",
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--n-db", "200", "--windows", "2", "--check", "--full",
            "--no-cpu-baseline", "--no-vqvae", "--no-prewarm", "--sharded-mixed-min-gflop", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -58,7 +58,7 @@ def test_bench_strong_and_multiclip(extra, scaling, clips):
     env = dict(os.environ, QPG_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "2", "--check", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "2", "--check", "--full", "--no-cpu-baseline",
            "--no-vqvae", "--no-prewarm", "--sharded-mixed-min-gflop", "0"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -73,8 +73,8 @@ def test_bench_sharded_small_shards_keep_the_f64_sweep():
     env = dict(os.environ, QPG_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-db", "200", "--windows", "2", "--check", "--no-cpu-baseline",
-           "--no-vqvae", "--no-prewarm"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-db", "200", "--windows", "2", "--check", "--full",
+           "--no-cpu-baseline", "--no-vqvae", "--no-prewarm"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -166,7 +166,7 @@ def test_sharded_path_over_rccl_with_one_rank():
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-db", "200",
-               "--windows", "2", "--check", "--no-cpu-baseline", "--no-vqvae", "--no-prewarm", "--no-cold"] + extra
+               "--windows", "2", "--check", "--full", "--no-cpu-baseline", "--no-vqvae", "--no-prewarm", "--no-cold"] + extra
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, str(extra) + r.stdout[-2000:] + r.stderr[-3000:]
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -184,7 +184,7 @@ def test_sharded_path_over_rccl_with_one_rank():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-db", "200",
-           "--windows", "2", "--check", "--no-cpu-baseline", "--no-vqvae", "--no-prewarm", "--no-cold",
+           "--windows", "2", "--check", "--full", "--no-cpu-baseline", "--no-vqvae", "--no-prewarm", "--no-cold",
            "--sharded-mixed-min-gflop", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

@@ -130,7 +130,8 @@ def _bench(world, extra, timeout=600):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "5", "--warmup", "2", "--check", "--no-cpu-baseline", "--no-vqvae"] + extra
+           "--gpus", str(world), "--steps", "5", "--warmup", "2", "--check", "--full", "--no-cpu-baseline",
+           "--no-vqvae"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

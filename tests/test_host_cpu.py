@@ -575,6 +575,7 @@ def test_bench_sub_records_commands_parse():
     for name, what, flags in b.SUB_RUNS:
         a = b.build_parser().parse_args(flags + b.SUB_COMMON)
         assert a.no_sub_records and a.gpus == 1 and a.no_cpu_baseline and a.steps >= 20 and what
+        assert a.full                  # (the records read the child's --full fields: eager leg, graph replay check, ...)
         got[name] = a
     assert got["cfg3"].workload == "cfg3"
     assert got["strong8192"].scaling == "strong" and got["strong8192"].n_db is None        # (strong: 8192 windows)
@@ -583,3 +584,22 @@ def test_bench_sub_records_commands_parse():
     assert got["clips16_f16_enc96_f16x3"].encode_precision == "f16x3"
     d = b.build_parser().parse_args([])                                                     # the driver's default run
     assert not d.no_sub_records and d.gpus == 1 and d.workload == "match"
+    assert not d.full and d.dump_outputs is None                                            # (a plain run: headline only)
+
+
+def test_bench_dump_outputs_writes_float64(tmp_path):
+    """bench.py --dump-outputs: every array as <DIR>/<name>.npy in float64 (integer codes exact), one file per rank with
+    N > 1 ranks, and no more than 64 MB in all."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    codes = np.arange(180, dtype=np.int32).reshape(6, 30) * 3
+    b.dump_outputs(str(tmp_path / "one"), {"codes": codes}, 1, 0)
+    got = np.load(tmp_path / "one" / "codes.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, codes)
+    b.dump_outputs(str(tmp_path / "two"), {"codes": codes}, 2, 1)
+    assert os.listdir(tmp_path / "two") == ["codes_rank1.npy"]
+    with pytest.raises(ValueError):
+        b.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((b.DUMP_LIMIT_BYTES // 8 + 1,), np.float32)}, 1, 0)

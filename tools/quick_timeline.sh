@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/q; mkdir -p $O; export TMPDIR=/tmp; R=$PWD
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout 600 python bench.py --no-f64-line > $O/bench.json 2> $O/bench.err
+  timeout 600 python bench.py --full --no-f64-line > $O/bench.json 2> $O/bench.err
   python -c "
 import json; d=json.load(open('$O/bench.json')); print({k:d[k] for k in ('value','ms_per_step')}, d['roofline'].get('kernel_ms'))"
 fi

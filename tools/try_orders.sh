@@ -7,7 +7,7 @@ for rep in 1 2 3; do
     [ $mode = text-first ] && fl="--text-first"
     [ $mode = audio-first ] && ev="QPG_BENCH_AUDIO_FIRST=1"
     [ $mode = after ] && ev="QPG_BENCH_AUDIO_FIRST=0"
-    env $ev python bench.py --no-f64-line --steps 400 $fl 2>/dev/null | python -c "
+    env $ev python bench.py --full --no-f64-line --steps 400 $fl 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$mode', d['ms_per_step'], d['roofline']['kernel_ms'])"
   done
 done
