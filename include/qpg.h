@@ -709,6 +709,47 @@ int qpg_pose_to_euler_f64(qpg_ctx*, void* stream, const float* poses, int64_t T,
                           const double* stdc, const double* sg_mid, const double* sg_head, const double* sg_tail, int W,
                           double* euler, int32_t* status);
 
+/* ---- Phase extraction: PAE inference (codebook/PAE.py:477-508 pose2phase, Model.forward :99-145 up to `params`) for
+ * every frame of many clips in one call.  Model: PAE.Model(135, 8, 240, 13, 4.0) in eval mode.
+ *   pose      [dev] f64 [n_total][135] the clips' `upper` rotation channels, concatenated;
+ *   clip_off  [dev] i64 [n_clips + 1] clip c is rows clip_off[c] .. clip_off[c+1]-1 (clip_off[0] = 0, clip_off[n_clips] =
+ *             n_total, non-decreasing: the caller's invariant); no window ever crosses a clip boundary;
+ *   mean, stdc [dev] f64 [135] codebook.yml's data_mean and clip(data_std, 0.01);
+ *   params    [dev] f32 [QPG_PAE_PARAM_FLOATS], packed by the host (qpgesture_amd/PAE.py:pack_params):
+ *     W1   at QPG_PAE_OFF_W1   [240 taps][34 channel groups][64 lanes] = conv1.weight[o = lane & 15][c = 4 group +
+ *          (lane >> 4)][tap] (0 for o = 15, c = 135): the B fragments of v_mfma_f32_16x16x4_f32;
+ *     BN1  at QPG_PAE_OFF_BN1  [3][16] conv1.bias, alpha = bn_conv1.weight / sqrt(running_var + 1e-5),
+ *          beta = bn_conv1.bias - running_mean * alpha (0 for o = 15): y = tanh((acc + bias) * alpha + beta);
+ *     W2   at QPG_PAE_OFF_W2   [240][4][64] = conv2.weight[e = lane & 15][o = 4 group + (lane >> 4)][tap] (0 for e >= 8,
+ *          o = 15);   BN2 at QPG_PAE_OFF_BN2 [3][16] as BN1 for conv2 / bn_conv2;
+ *     FC   at QPG_PAE_OFF_FC   [8][2][240] fc[e].weight;  FCBN at QPG_PAE_OFF_FCBN [3][16] fc[e].bias, bn[e] alpha,
+ *          beta at index 2 e + j;   FREQ at QPG_PAE_OFF_FREQ [120] the model's `freqs`;  TPI at QPG_PAE_OFF_TPI [1].
+ * Frames frame0 .. frame0 + n_frames - 1 of the concatenation are computed (n_frames <= QPG_PAE_MAX_CHUNK);
+ * out [dev] f32 [n_frames][4][8] = [p, f, a, b] x 8 channels (the reference's (T,4,1,8,1) array); v_out: optional [dev]
+ * f32 [n_frames][8][2] the BN'd fc output (x, y) that p is the atan2' of; latent_out: optional [dev] f32
+ * [n_frames][8][240].  ws: [dev] f32 scratch of at least (n_frames + 2 QPG_PAE_HALO - 1) * QPG_PAE_WS_STRIDE floats
+ * (the f32 velocities of the rows the chunk reads).  A frame's result does not depend on frame0, n_frames or the
+ * other clips (bit-identical however a batch is chunked).  n_frames = 0 is a no-op. */
+#define QPG_PAE_CHANNELS 135
+#define QPG_PAE_MID 15
+#define QPG_PAE_EMBED 8
+#define QPG_PAE_TIME 240
+#define QPG_PAE_HALO 120
+#define QPG_PAE_WS_STRIDE 136
+#define QPG_PAE_MAX_CHUNK (1 << 22)
+#define QPG_PAE_OFF_W1 0
+#define QPG_PAE_OFF_BN1 522240
+#define QPG_PAE_OFF_W2 522288
+#define QPG_PAE_OFF_BN2 583728
+#define QPG_PAE_OFF_FC 583776
+#define QPG_PAE_OFF_FCBN 587616
+#define QPG_PAE_OFF_FREQ 587664
+#define QPG_PAE_OFF_TPI 587784
+#define QPG_PAE_PARAM_FLOATS 587792
+int qpg_pae_phase_f32(qpg_ctx*, void* stream, const float* params, const double* pose, const double* mean,
+                      const double* stdc, const int64_t* clip_off, int n_clips, int64_t n_total, int64_t frame0,
+                      int64_t n_frames, float* ws, int64_t ws_floats, float* out, float* v_out, float* latent_out);
+
 /* ---- VQ-VAE training step (codebook/train.py:120-148): VQVAE.forward's loss terms, the bottleneck statistics,
  * the EMA codebook update, the loss gradient and Adam.  Reductions are ordered two-stage sums in f64
  * (deterministic).  `ws` is a caller-owned scratch of at least qpg_vq_reduce_ws_bytes() bytes. ---- */

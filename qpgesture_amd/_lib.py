@@ -88,6 +88,7 @@ _SIGS = {
     "qpg_tpack_f32": [P, I, I, I, I, P],
     "qpg_resblock_f32": [P, I, I, I, P, P, P, P, P],
     "qpg_pose_to_euler_f64": [P, L, I, P, P, P, P, P, I, P, P],
+    "qpg_pae_phase_f32": [P, P, P, P, P, I, L, L, L, P, L, P, P, P],
     "qpg_vq_argmin_f32": [P, P, P, L, I, I, P, P, P],
     "qpg_vq_gather_f32": [P, P, L, I, I, P, P],
     "qpg_vq_encode_f32": [P, P, I, I, P, L, P, P, P],

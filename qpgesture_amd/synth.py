@@ -258,3 +258,70 @@ def make_vqvae_state_dict(seed, hps=None, prefix="module."):
     conv("decoders.0.out", Cin, E, 3)
     sd[prefix + "bottleneck.level_blocks.0.k"] = rng.standard_normal((K, E)).astype(np.float32)
     return sd
+
+
+# ----------------------------------------------------------------------------------------------
+# Periodic Auto-Encoder (DeepPhase, codebook/PAE.py): seeded weights with the reference's key names
+# ----------------------------------------------------------------------------------------------
+PAE_HPS = dict(input_channels=135, embedding_channels=8, time_range=240, key_range=13, window=4.0)
+
+
+def make_pae_state_dict(seed, prefix=""):
+    """No PAE checkpoint ships with the reference either.  Seeded PAE.Model(135, 8, 240, 13, 4.0) weights with the
+    reference's key names and shapes (the reference saves the bare model's state_dict: no `module.`).  The batch-norm
+    layers get non-trivial running statistics and affine parameters, scaled so that on smooth unit-amplitude
+    normalised motion (make_pae_motion) both tanh layers work mostly in their non-saturated range."""
+    rng = _rng(seed)
+    C, E, T = PAE_HPS["input_channels"], PAE_HPS["embedding_channels"], PAE_HPS["time_range"]
+    M = C // 9
+    ts = PAE_HPS["key_range"] / T
+    sd = {}
+
+    def f32(a):
+        return np.ascontiguousarray(a, np.float32)
+
+    def conv(name, cout, cin, gain):
+        sd[prefix + name + ".weight"] = f32(rng.standard_normal((cout, cin, T)) * gain / np.sqrt(cin * T))
+        sd[prefix + name + ".bias"] = f32(rng.standard_normal(cout) * 0.05)
+
+    def bn(name, n, mean_scale, var_scale):
+        sd[prefix + name + ".weight"] = f32(rng.uniform(0.6, 1.4, n) * rng.choice([-1.0, 1.0], n))
+        sd[prefix + name + ".bias"] = f32(rng.standard_normal(n) * 0.1)
+        sd[prefix + name + ".running_mean"] = f32(rng.standard_normal(n) * mean_scale)
+        sd[prefix + name + ".running_var"] = f32(rng.uniform(0.5, 2.0, n) * var_scale)
+        sd[prefix + name + ".num_batches_tracked"] = np.array(1000, np.int64)
+
+    sd[prefix + "tpi"] = np.array([2.0 * np.pi], np.float32)
+    sd[prefix + "args"] = np.linspace(-PAE_HPS["window"] / 2, PAE_HPS["window"] / 2, T, dtype=np.float32)
+    sd[prefix + "freqs"] = f32(np.fft.rfftfreq(T)[1:] * (T * ts) / PAE_HPS["window"])
+    conv("conv1", M, C, 6.0)
+    bn("bn_conv1", M, 0.05, 0.6)
+    conv("conv2", E, M, 2.0)
+    bn("bn_conv2", E, 0.05, 0.5)
+    for i in range(E):
+        sd[prefix + "fc.%d.weight" % i] = f32(rng.standard_normal((2, T)) / np.sqrt(T) * 3.0)
+        sd[prefix + "fc.%d.bias" % i] = f32(rng.standard_normal(2) * 0.05)
+        bn("bn.%d" % i, 2, 0.05, 0.5)
+    conv("deconv1", M, E, 1.0)
+    bn("bn_deconv1", M, 0.05, 1.0)
+    conv("deconv2", C, M, 1.0)
+    return sd
+
+
+def make_pae_motion(T, seed, still=None):
+    """(T, 135) f64 smooth synthetic `upper` rotation channels: mean + std * (unit-amplitude sum of sinusoids with
+    0.5-4 s periods at 60 fps), so that the normalised motion is O(1) and its velocities O(0.05).  `still` = (a, b):
+    frames a..b-1 hold frame a's pose (a stretch of zero velocity)."""
+    from .checkpoint import load_config
+    cfg = load_config(os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs", "codebook.yml"))
+    mean, std = np.asarray(cfg.data_mean, np.float64), np.clip(np.asarray(cfg.data_std, np.float64), 0.01, None)
+    rng = _rng(seed)
+    t = np.arange(T, dtype=np.float64)[:, None]
+    sig = np.zeros((T, mean.shape[0]))
+    for _ in range(3):
+        period = rng.uniform(30.0, 240.0, mean.shape[0])
+        sig += rng.uniform(0.2, 0.6, mean.shape[0]) * np.sin(2 * np.pi * t / period + rng.uniform(0, 2 * np.pi, mean.shape[0]))
+    if still is not None:
+        a, b = still
+        sig[a:b] = sig[a]
+    return mean + std * sig
