@@ -777,16 +777,23 @@ int qpg_vq_commit_grad_f32(qpg_ctx*, void* stream, const float* z, const float* 
 
 /* BottleneckBlock.update_k (bottleneck.py:63-94) in two halves so that the caller can all-reduce the batch sums
  * across ranks in between (bottleneck.py:73-75):
- *   qpg_vq_code_sums_f32: batch_sum[c][:] = sum of z rows assigned to c (ascending row order), batch_elem[c] = count;
+ *   qpg_vq_code_sums_f32: batch_sum[c][:] = sum of z rows assigned to c, batch_elem[c] = count (exact).  Order, fixed
+ *   and so run-to-run bit-identical: the rows are taken in chunks of 1024; within a chunk a code's rows are added in
+ *   ascending row order (f32, from +0), then the partials of the chunks holding rows of the code are added in chunk
+ *   order (f32, from +0).  For a code spanning several chunks this is not the plain ascending-row f32 sum;
  *   qpg_vq_ema_update_f32: k_sum/k_elem EMA (mu), k = k_sum/k_elem where k_elem >= threshold else k_rand; also
  *   refreshes kT ([E][ldkT] transposed copy, optional) and kk ([K] squared norms, optional) used by the quantiser,
- *   out4 [dev] f32 = {entropy, used_curr, usage, dk}.  ws: >= K doubles. */
+ *   out4 [dev] f32 = {entropy, used_curr, usage, dk}.  ws: >= K doubles.
+ * kk[c] is sum_e k[c][e]^2 accumulated in f64 and rounded once to f32; qpg_vq_code_norms_f32 computes it for a given
+ * k (K x E) with exactly the same arithmetic (VQVAE uses it after init_k and when it loads a checkpoint), so such a
+ * codebook gets the kk an EMA step would have left. */
 int64_t qpg_vq_code_sums_ws_bytes(int64_t R, int E, int K);
 int qpg_vq_code_sums_f32(qpg_ctx*, void* stream, const float* z, const int64_t* ids, int64_t R, int E, int K,
                          float* batch_sum, float* batch_elem, void* ws, int64_t ws_bytes);
 int qpg_vq_ema_update_f32(qpg_ctx*, void* stream, float* k, float* k_sum, float* k_elem, const float* batch_sum,
                           const float* batch_elem, const float* k_rand, float mu, float threshold, int K, int E,
                           float* kT, int ldkT, float* kk, void* ws, int64_t ws_bytes, float* out4);
+int qpg_vq_code_norms_f32(qpg_ctx*, void* stream, const float* k, int K, int E, float* kk);
 
 /* torch.optim.Adam single step as train.py:71 configures it (no weight decay / amsgrad), over a flat buffer. */
 int qpg_adam_step_f32(qpg_ctx*, void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

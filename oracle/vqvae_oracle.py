@@ -105,16 +105,17 @@ def losses(x_target, x_out, commit_loss, hps_commit=0.02, vel=1.0, acc=1.0, reg=
 
 def ema_update(x, x_l, k, k_sum, k_elem, k_rand, mu=0.99, threshold=1.0):
     """BottleneckBlock.update_k (bottleneck.py:63-94) given the random-restart rows `k_rand` (the reference draws
-    them with y[t.randperm(n)][:k_bins]).  x (R,E), x_l (R,) int64.  Returns new (k, k_sum, k_elem) and the metrics."""
+    them with y[t.randperm(n)][:k_bins]).  x (R,E), x_l (R,) int64.  Returns new (k, k_sum, k_elem) and the metrics.
+    Computes in x's dtype (float64 inputs give the float64 reference of the EMA kernel)."""
     k_bins, E = k.shape
-    onehot = torch.zeros(k_bins, x.shape[0])
+    onehot = torch.zeros(k_bins, x.shape[0], dtype=x.dtype)
     onehot.scatter_(0, x_l.view(1, -1), 1)
     _k_sum = torch.matmul(onehot, x)
     _k_elem = onehot.sum(dim=-1)
     old_k = k
     k_sum = mu * k_sum + (1. - mu) * _k_sum
     k_elem = mu * k_elem + (1. - mu) * _k_elem
-    usage = (k_elem.view(k_bins, 1) >= threshold).float()
+    usage = (k_elem.view(k_bins, 1) >= threshold).to(k_sum.dtype)
     k_new = usage * (k_sum.view(k_bins, E) / k_elem.view(k_bins, 1)) + (1 - usage) * k_rand
     _k_prob = _k_elem / torch.sum(_k_elem)
     entropy = -torch.sum(_k_prob * torch.log(_k_prob + 1e-8))

@@ -99,6 +99,7 @@ _SIGS = {
     "qpg_vq_commit_grad_f32": [P, P, L, I, c_float, P, P],
     "qpg_vq_code_sums_f32": [P, P, L, I, I, P, P, P, L],
     "qpg_vq_ema_update_f32": [P, P, P, P, P, P, c_float, c_float, I, I, P, I, P, P, L, P],
+    "qpg_vq_code_norms_f32": [P, I, I, P],
     "qpg_conv1d_bwd_data_f32": [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P, L],
     "qpg_conv1d_bwd_weight_f32": [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, L],
     "qpg_adam_step_f32": [P, P, P, P, L, c_float, c_float, c_float, c_float, L],

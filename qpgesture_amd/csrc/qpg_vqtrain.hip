@@ -266,8 +266,9 @@ __global__ __launch_bounds__(256) void vq_code_sums_reduce_kernel(const float* _
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t n = (int64_t)K * E;
   if (i < n) {
-    // chunks that hold no row of the code contribute an exact +0: skipping them keeps the sum identical to the
-    // plain ascending-row sum
+    // the chunk partials (each an ascending-row f32 sum from +0) are added in chunk order from +0; chunks that hold
+    // no row of the code are skipped.  Not the plain ascending-row sum over all rows once a code spans chunks: every
+    // partial is rounded on its own
     float v = 0.f;
     const int c = (int)(i / E);
     for (int s = 0; s < S; ++s)
@@ -278,6 +279,25 @@ __global__ __launch_bounds__(256) void vq_code_sums_reduce_kernel(const float* _
     int t = 0;
     for (int s = 0; s < S; ++s) t += part_n[(size_t)s * K + c];
     kelem[c] = (float)t;
+  }
+}
+
+// sums a and b over a 128-thread block (wave trees, then wave 0 + wave 1); the results are valid in thread 0
+__device__ __forceinline__ void block128_sum2(double& a, double& b) {
+  __shared__ double sm[2][2];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_down(a, o, 64);
+    b += __shfl_down(b, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sm[threadIdx.x >> 6][0] = a;
+    sm[threadIdx.x >> 6][1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = sm[0][0] + sm[1][0];
+    b = sm[0][1] + sm[1][1];
   }
 }
 
@@ -307,21 +327,24 @@ __global__ __launch_bounds__(128) void vq_ema_apply_kernel(float* __restrict__ k
   }
   __syncthreads();
   if (threadIdx.x == 0) k_elem[c] = ne;
-  __shared__ double sm[2][2];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    d2 += __shfl_down(d2, o, 64);
-    n2 += __shfl_down(n2, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sm[threadIdx.x >> 6][0] = d2;
-    sm[threadIdx.x >> 6][1] = n2;
-  }
-  __syncthreads();
+  block128_sum2(d2, n2);
   if (threadIdx.x == 0) {
-    dk2[c] = sm[0][0] + sm[1][0];
-    if (kk) kk[c] = (float)(sm[0][1] + sm[1][1]);
+    dk2[c] = d2;
+    if (kk) kk[c] = (float)n2;
   }
+}
+
+// kk[c] = |k[c]|^2 exactly as vq_ema_apply_kernel computes it (same per-thread f64 partials, same block reduction, one
+// rounding to f32): the quantiser's kk after init_k / a checkpoint restore is bit-identical to the one an EMA step leaves
+__global__ __launch_bounds__(128) void vq_code_norms_kernel(const float* __restrict__ k, int E, float* __restrict__ kk) {
+  const int c = blockIdx.x;
+  double n2 = 0.0, unused = 0.0;
+  for (int e = threadIdx.x; e < E; e += 128) {
+    const float v = k[(size_t)c * E + e];
+    n2 += (double)v * (double)v;
+  }
+  block128_sum2(unused, n2);
+  if (threadIdx.x == 0) kk[c] = (float)n2;
 }
 
 // one block: out[4] = {entropy, used_curr, usage, dk}   (bottleneck.py:80-86)
@@ -697,6 +720,13 @@ extern "C" int qpg_vq_ema_update_f32(qpg_ctx* ctx, void* stream, float* k, float
   hipLaunchKernelGGL(vq_ema_stats_kernel, dim3(1), dim3(RED_THREADS), 0, qpg_stream(stream), batch_elem, k_elem,
                      (const double*)ws, threshold, K, E, out4);
   QPG_LAUNCH_CHECK("vq_ema_stats_kernel");
+  return QPG_OK;
+}
+
+extern "C" int qpg_vq_code_norms_f32(qpg_ctx* ctx, void* stream, const float* k, int K, int E, float* kk) {
+  QPG_REQUIRE(ctx && k && kk && K > 0 && E > 0, "qpg_vq_code_norms_f32: bad argument");
+  hipLaunchKernelGGL(vq_code_norms_kernel, dim3(K), dim3(128), 0, qpg_stream(stream), k, E, kk);
+  QPG_LAUNCH_CHECK("vq_code_norms_kernel");
   return QPG_OK;
 }
 

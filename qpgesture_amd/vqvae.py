@@ -126,7 +126,8 @@ class VQVAE:
         k = sd["bottleneck.level_blocks.0.k"]                   # (bins, emb)
         self.k = k.to(dev).contiguous()
         self.kT = _Conv(k.t().contiguous()[None], torch.zeros(self.bins), dev)      # x.k^T as a 1-tap "conv"
-        self.kk = torch.sum(k.t() ** 2, dim=0).to(dev).contiguous()                # bottleneck.py:123
+        self.kk = torch.empty((self.bins,), dtype=torch.float32, device=dev)      # |k|^2 (bottleneck.py:123)
+        self._code_norms()
         self._flatten_parameters()
         self._tpack_all()
         self._desc = self._build_descriptor()
@@ -603,11 +604,17 @@ class VQVAE:
         _lib.call("qpg_vq_gather_f32", self.device, table, idx, idx.numel(), table.shape[1], table.shape[0], out, None)
         return out
 
+    def _code_norms(self):
+        """kk = |k|^2 by the EMA kernel's own arithmetic (qpg_vq_code_norms_f32): the quantiser sees the same kk whether
+        the codebook came from an EMA update, from init_k or from a checkpoint (an f32 torch.sum can differ in the last
+        bit and move a near-tie)."""
+        _lib.call("qpg_vq_code_norms_f32", self.device, self.k, self.bins, self.emb, self.kk)
+
     def _refresh_quantiser(self):
-        """kT / kk follow k (after init_k or a checkpoint restore)."""
+        """kT / kk follow k (after init_k)."""
         self._tpack_stale = True
         self.kT.w[0, :self.emb, :self.bins].copy_(self.k.t())
-        self.kk.copy_(torch.sum(self.k.t() ** 2, dim=0))
+        self._code_norms()
 
     def _init_k(self, z2):
         """BottleneckBlock.init_k (bottleneck.py:39-49): k <- random rows of the first batch (tiled with noise when the
