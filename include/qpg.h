@@ -750,6 +750,67 @@ int qpg_pae_phase_f32(qpg_ctx*, void* stream, const float* params, const double*
                       const double* stdc, const int64_t* clip_off, int n_clips, int64_t n_total, int64_t frame0,
                       int64_t n_frames, float* ws, int64_t ws_floats, float* out, float* v_out, float* latent_out);
 
+/* ---- PAE training (codebook/PAE.py:273-476): one step of Model(135, 8, 240, 13, 4.0) on a batch of windows.
+ *   params [dev] f32 [QPG_PAET_PARAM_FLOATS]: every parameter of the model, flat, in named_parameters() order
+ *     (row-major torch shapes):  tpi [1] at QPG_PAET_OFF_TPI, args [240] at _ARGS, freqs [120] at _FREQS (these three
+ *     are constants: no gradient, no update), conv1.weight (15, 135, 240) at _CONV1_W, conv1.bias [15] at _CONV1_B,
+ *     bn_conv1.weight [15] | .bias [15] at _BN1, conv2.weight (8, 15, 240) at _CONV2_W, conv2.bias [8] at _CONV2_B,
+ *     bn_conv2.weight [8] | .bias [8] at _BN2, fc.e.weight (2, 240) | fc.e.bias [2] at _FC + 482 e, bn.e.weight [2]
+ *     | bn.e.bias [2] at _FCBN + 4 e, deconv1.weight (15, 8, 240) at _DECONV1_W, deconv1.bias [15] at _DECONV1_B,
+ *     bn_deconv1.weight [15] | .bias [15] at _BN3, deconv2.weight (135, 15, 240) at _DECONV2_W, deconv2.bias [135]
+ *     at _DECONV2_B.  The trainable parameters are the contiguous range from QPG_PAET_TRAINABLE to the end.
+ *   grads  [dev] f32, the same layout (entries below QPG_PAET_TRAINABLE are left untouched).
+ *   stats  [dev] f32 [QPG_PAET_STATS_FLOATS] BatchNorm running statistics: running_mean | running_var of bn_conv1
+ *     at QPG_PAET_ST_BN1 (15 | 15), bn_conv2 at _ST_BN2 (8 | 8), bn.e at _ST_FCBN + 4 e (2 | 2), bn_deconv1 at
+ *     _ST_BN3 (15 | 15).  num_batches_tracked is the caller's count of training forwards.
+ *   poses  [dev] f32 [n_frames][135]: normalised poses (pose - mean) / clip(std, 0.01) in f64, rounded once, of one
+ *     or many clips concatenated;  starts [dev] i64 [batch]: window b is poses[starts[b] .. starts[b] + 239] (the
+ *     caller keeps windows inside their clip; a start outside 0 .. n_frames - 240 yields a NaN window).
+ *   ws     [dev] f32 scratch of qpg_pae_train_ws_floats(batch) floats, 16-byte aligned.  The forward leaves every
+ *     activation there for the backward of the same batch; nothing is allocated and nothing waits for the host. */
+#define QPG_PAET_OFF_TPI 0
+#define QPG_PAET_OFF_ARGS 1
+#define QPG_PAET_OFF_FREQS 241
+#define QPG_PAET_TRAINABLE 361
+#define QPG_PAET_OFF_CONV1_W 361
+#define QPG_PAET_OFF_CONV1_B 486361
+#define QPG_PAET_OFF_BN1 486376
+#define QPG_PAET_OFF_CONV2_W 486406
+#define QPG_PAET_OFF_CONV2_B 515206
+#define QPG_PAET_OFF_BN2 515214
+#define QPG_PAET_OFF_FC 515230
+#define QPG_PAET_OFF_FCBN 519086
+#define QPG_PAET_OFF_DECONV1_W 519118
+#define QPG_PAET_OFF_DECONV1_B 547918
+#define QPG_PAET_OFF_BN3 547933
+#define QPG_PAET_OFF_DECONV2_W 547963
+#define QPG_PAET_OFF_DECONV2_B 1033963
+#define QPG_PAET_PARAM_FLOATS 1034098
+#define QPG_PAET_ST_BN1 0
+#define QPG_PAET_ST_BN2 30
+#define QPG_PAET_ST_FCBN 46
+#define QPG_PAET_ST_BN3 78
+#define QPG_PAET_STATS_FLOATS 108
+#define QPG_PAET_MAX_BATCH 65536
+#define QPG_PAET_SLABS 16            /* weight gradients: windows split into min(batch, 16) slabs, added in order */
+/* floats [host] i64: the scratch floats a batch of 2 .. QPG_PAET_MAX_BATCH windows needs (refused outside). */
+int qpg_pae_train_ws_floats(qpg_ctx*, void* stream, int batch, int64_t* floats);
+/* Forward of a batch: train = 1 is training mode (zero velocity row first, BatchNorm over the batch, running
+ * statistics updated, dL/dy kept in ws for the backward); train = 0 is eval mode (zero row last, the running
+ * statistics; nothing is updated).  loss: optional [dev] f64 scalar, 300 * mean((y - x)^2).  batch >= 2. */
+int qpg_pae_train_forward_f32(qpg_ctx*, void* stream, const float* params, float* stats, const float* poses,
+                              int64_t n_frames, const int64_t* starts, int batch, int train, float* ws,
+                              int64_t ws_floats, double* loss);
+/* Backward of the last training-mode forward on ws (same params, same batch): every trainable gradient into grads
+ * (overwritten, not accumulated). */
+int qpg_pae_train_backward_f32(qpg_ctx*, void* stream, const float* params, int batch, float* ws, int64_t ws_floats,
+                               float* grads);
+/* AdamW of Library/AdamWR/adamw.py on n f32 values: p = p * (1 - weight_decay) (weight decay not scaled by lr), then
+ * m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2, p -= step_size * m / (sqrt(v) + eps) with step_size =
+ * lr sqrt(1 - beta2^step) / (1 - beta1^step).  step >= 1 counts this update.  (qpg_adam_step_f32 is torch.optim.Adam.) */
+int qpg_pae_adamw_f32(qpg_ctx*, void* stream, float* p, const float* g, float* m, float* v, int64_t n, double lr,
+                      double weight_decay, double beta1, double beta2, double eps, int64_t step);
+
 /* ---- VQ-VAE training step (codebook/train.py:120-148): VQVAE.forward's loss terms, the bottleneck statistics,
  * the EMA codebook update, the loss gradient and Adam.  Reductions are ordered two-stage sums in f64
  * (deterministic).  `ws` is a caller-owned scratch of at least qpg_vq_reduce_ws_bytes() bytes. ---- */

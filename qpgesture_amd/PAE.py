@@ -7,7 +7,8 @@ the device.
 
 turns every `<rotation_dir>/<name>.npz['upper']` (T, 135) into `<phase_dir>/<name>.npz['phase']` float32 (T, 4, 1, 8, 1)
 = [p, f, a, b] per frame (PAE.py:536-565), skipping files that exist.  Same flags as codebook/configs/parse_args.py; the
-defaults of the three path flags (additive) are the reference's hard-coded paths.  `--stage train` is out of scope.
+defaults of the three path flags (additive) are the reference's hard-coded paths.  `--stage train` (PAE
+training) is `python -m qpgesture_amd.PAE_train`.
 
 The reference runs Model.forward once per frame on a 240-frame window (PAE.py:477-508); here every frame of many clips
 goes through one C-ABI call (qpg_pae_phase_f32, csrc/qpg_pae.hip): velocities on the device in f64, conv1 / conv2 on the
@@ -213,8 +214,8 @@ def main(argv=None):
     from .checkpoint import load_config
     args = build_parser().parse_args(argv)
     if args.stage != "inference":
-        raise SystemExit("only --stage inference (phase extraction) is implemented; PAE training (--stage %s) is out "
-                         "of scope" % args.stage)
+        raise SystemExit("this module runs --stage inference (phase extraction) only; --stage %s is out of scope "
+                         "here: PAE training is `python -m qpgesture_amd.PAE_train`" % args.stage)
     return inference(args.PAE_model_path, args.rotation_dir, args.phase_dir, load_config(args.config), gpu=args.gpu,
                      chunk=args.chunk)
 

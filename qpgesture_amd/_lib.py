@@ -89,6 +89,10 @@ _SIGS = {
     "qpg_resblock_f32": [P, I, I, I, P, P, P, P, P],
     "qpg_pose_to_euler_f64": [P, L, I, P, P, P, P, P, I, P, P],
     "qpg_pae_phase_f32": [P, P, P, P, P, I, L, L, L, P, L, P, P, P],
+    "qpg_pae_train_ws_floats": [I, P],
+    "qpg_pae_train_forward_f32": [P, P, P, L, P, I, I, P, L, P],
+    "qpg_pae_train_backward_f32": [P, I, P, L, P],
+    "qpg_pae_adamw_f32": [P, P, P, P, L, c_double, c_double, c_double, c_double, c_double, L],
     "qpg_vq_argmin_f32": [P, P, P, L, I, I, P, P, P],
     "qpg_vq_gather_f32": [P, P, L, I, I, P, P],
     "qpg_vq_encode_f32": [P, P, I, I, P, L, P, P, P],

@@ -13,7 +13,7 @@ void qpg_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int qpg_version(void) { return 108; }          // 1.08: qpg_pae_phase_f32 (phase extraction)
+extern "C" int qpg_version(void) { return 109; }          // 1.09: PAE training (qpg_pae_train_*, qpg_pae_adamw_f32)
                                                           // 1.07: round 6 (qpg_build_id, qpg_ctx_set_option; the qpg_debug_* setters left the product: include/qpg.h)
 
 // The SHA-256 (first 16 hex digits) of the sources this library was compiled from - csrc/*.hip, csrc/*.h, include/qpg.h in
