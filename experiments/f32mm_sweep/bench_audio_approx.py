@@ -14,7 +14,7 @@ if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(os.path
                            os.path.join(ROOT, "qpgesture_amd", "csrc", "qpg_core.hip"), "-o", SO])
 exp = ctypes.CDLL(SO)
 P_, I_, L_ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-exp.qpg_ctx_create.argtypes = [I_, ctypes.POINTER(P_)]
+exp.qpg_ctx_create.argtypes = _lib.prototypes()["qpg_ctx_create"].argtypes       # (declared in include/qpg.h)
 exp.qpg_audio_cosine_approx_f32.argtypes = [P_, P_, P_, I_, I_, I_, P_, I_, I_, I_, P_, P_, P_, I_, P_, L_]
 exp.qpg_audio_cosine_approx_lds.argtypes = [P_, P_, P_, I_, I_, I_, P_, I_, I_, I_, P_, P_, P_, I_, P_, L_]
 _ectx = P_(); assert exp.qpg_ctx_create(0, ctypes.byref(_ectx)) == 0

@@ -16,7 +16,7 @@ exp = ctypes.CDLL(SO)
 P, I, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 exp.qpg_i8_slice_rows.argtypes = [P, P, P, L, I, P, P, P]
 exp.qpg_audio_cosine_i8.argtypes = [P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, P, L]
-exp.qpg_ctx_create.argtypes = [I, ctypes.POINTER(P)]
+exp.qpg_ctx_create.argtypes = _lib.prototypes()["qpg_ctx_create"].argtypes       # (declared in include/qpg.h)
 _ectx = P(); assert exp.qpg_ctx_create(0, ctypes.byref(_ectx)) == 0
 def ecall(name, dev, *args):
     st = P(torch.cuda.current_stream(dev).cuda_stream)

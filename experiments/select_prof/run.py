@@ -8,7 +8,6 @@ runpy.run_path(os.path.join(root, "tools", "step_loop.py"), run_name="__main__")
 from qpgesture_amd import _lib
 lib = _lib.load()
 buf = (ctypes.c_longlong * 96)()
-lib.qpg_debug_select_prof.argtypes = [ctypes.c_void_p]
 assert lib.qpg_debug_select_prof(buf) == 0
 names = {0: "init", 1: "pass 1 (stream)", 2: "pass 2 (pot list)", 3: "list (a) + v", 4: "rank_pass(false)", 5: "list (b)",
          6: "park", 7: "phase 2 load", 8: "tier 1/2 merge + tables", 9: "rank_pass(true)", 10: "rank-level tie scan",

@@ -3,6 +3,7 @@
 The library is the product: if it is missing or a call fails this module raises —
 there is no CPU or PyTorch fallback anywhere in the package.
 """
+import collections
 import ctypes
 import os
 import re
@@ -17,109 +18,82 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "qpg.h")
 _lib = None
 _ctx = {}
 
-c_void_p, c_int, c_int64, c_double, c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                               ctypes.c_double, ctypes.c_float)
-P, I, L = c_void_p, c_int, c_int64
+c_void_p = ctypes.c_void_p
 
-# name -> argtypes (after ctx, stream)
-_SIGS = {
-    "qpg_signal_i32": [P, ctypes.c_int32],
-    "qpg_doorbell_wait": [P, P, ctypes.c_int32],
-    "qpg_wavlm_resample_f32": [P, L, I, I, I, P],
-    "qpg_frame_norm2_f64": [P, L, I, P],
-    "qpg_audio_cand_norm2": [P, I, I, P, I, I, I, P],
-    "qpg_l2_normalize_rows_f32": [P, L, I, P],
-    "qpg_text_pack_queries_f32": [P, I, I, I, P, P, I, P],
-    "qpg_audio_pack_queries": [P, I, I, I, P, P, I, I, I, P, P],
-    "qpg_audio_cosine_f64": [P, I, I, I, P, I, I, I, P, P, P, I, P, L],
-    "qpg_audio_cosine_f64_h": [P, I, I, I, P, I, I, I, P, P, P, I, P, L],
-    "qpg_audio_cosine_mx": [P, I, I, I, P, I, I, I, P, P, P, I, P, I, L, P],
-    "qpg_audio_cosine_mx_h": [P, I, I, I, P, I, I, I, P, P, P, I, P, I, L, P],
-    "qpg_audio_hl_pack_db": [P, I, I, I, I, I, I, I, P, L],
-    "qpg_audio_hl_pack_queries": [P, I, I, P, L],
-    "qpg_audio_pack_queries_hl": [P, I, I, I, P, P, I, I, I, P, P, P, L],
-    "qpg_clip_pack_hl": [P, I, I, I, P, P, I, I, I, P, P, P, L, P, I, I, I, P, P, I, P, P, L],
-    "qpg_audio_cosine_hl": [P, I, I, I, P, P, P, I, P, I, L, P],
-    "qpg_audio_hl1_pack_db": [P, I, I, I, I, I, I, I, P, L],
-    "qpg_audio_cosine_hl1": [P, I, I, I, P, P, P, I, P, I, L, P],
-    "qpg_probe_mfma_f16_tile": [P, P, P, I, P],
-    "qpg_hl_pack_rows": [P, L, I, P, L],
-    "qpg_hl_pack_cols": [P, I, I, P, L],
-    "qpg_hl_prepare_queries": [P, I, I, P, P, L, P],
-    "qpg_hl_gemm_distance": [P, L, I, P, I, P, L, P, L],
-    "qpg_percode_select_sorted_f32": [P, L, P, P, L, I, L, P, P, P, P, I, c_float, P, P, I, c_float, P, P, P, P, P,
-                                      ctypes.c_int32, I, L],
-    "qpg_hl_gemm_tilemin": [P, L, I, P, I, c_float, P, P, L],
-    "qpg_hl_gemm_tilemin_h": [P, L, I, P, I, c_float, P, P, L],
-    "qpg_perm32_rows_f32": [P, L, I, P],
-    "qpg_percode_select_bycode_f32": [P, P, L, I, L, P, P, P, P, I, c_float, P, P, I, c_float, P, P, P, P, P, I],
-    "qpg_text_pack_candidates_f32": [P, I, I, I, P, I, P],
-    "qpg_text_cosine_f32": [P, L, I, P, I, P, L],
-    "qpg_text_percode_f32": [P, L, I, P, I, P, I, I, ctypes.c_int32, c_float, P, L, P, P, P, P],
-    "qpg_text_pack_candidates_f16": [P, I, I, I, P, I, P, P],
-    "qpg_text_percode_f16": [P, P, L, I, P, I, P, I, ctypes.c_int32, c_float, P, L, P, P, P, P],
-    "qpg_percode_select_f64": [P, L, I, P, L, I, c_double, ctypes.c_int32, P, P, P, I, L],
-    "qpg_percode_select_f32": [P, L, I, P, L, I, c_float, ctypes.c_int32, P, P, P, I, L],
-    "qpg_percode_select_guarded_f64": [P, L, I, P, L, I, c_double, ctypes.c_int32, P, P, P, I, L, P, I, I, P, I, I, I, P,
-                                       c_double, P, I],
-    "qpg_percode_select_mixed_f64": [P, I, L, I, P, L, I, c_double, ctypes.c_int32, P, P, P, I, L, P, I, I, P, I, I, I, P,
-                                     P, P, c_double, c_double, P, P, L, I],
-    "qpg_percode_select_mixed_f64_cut": [P, I, L, I, P, L, I, c_double, ctypes.c_int32, P, P, P, I, L, P, I, I, P, I, I, I,
-                                         P, P, P, c_double, c_double, P, P, L, I, P, P, I, I],
-    "qpg_percode_select_exact_f64": [P, L, I, P, L, I, c_double, ctypes.c_int32, P, P, P, I, L, P, I, I, P, I, I, I, P,
-                                     c_double, P, I, P, L],
-    "qpg_merge_mixed_phase1_f64": [P, I, L, L, L, I, I, c_double, c_double, I, P, L, P, L, P, I, L],
-    "qpg_shard_refine_f64": [P, I, L, I, I, L, P, I, I, I, P, I, I, I, P, P, P, P, L, I, P, I],
-    "qpg_flags_stamp": [P, I, L, L, P],
-    "qpg_flags_gather": [P, I, L, L, P],
-    "qpg_merge_mixed_phase2_f64": [P, I, L, L, I, I, c_double, P, L, P, L, P, P, P, P, I, c_double],
-    "qpg_merge_select_f64": [P, I, L, L, L, I, I, c_double, P, P, P, c_double, P],
-    "qpg_merge_select_f32": [P, I, L, L, L, I, I, c_float, P, P, P],
-    "qpg_rank_rows_f64": [P, I, I, P],
-    "qpg_rank_rows_f32": [P, I, I, P],
-    "qpg_l2_table_f32": [P, I, I, P],
-    "qpg_wavvq_lev_f32": [P, I, I, P, I, P, I, P, I, I, P, P, I, P, L],
-    "qpg_conv1d_f32": [P, I, I, I, P, P, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P, P, L],
-    "qpg_convt_f32": [P, I, I, I, P, P, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
-    "qpg_convt_pair_f32": [P, I, I, I, P, P, I, I, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
-    "qpg_pad_channels_f32": [P, L, I, I, P],
-    "qpg_conv16_pack_weights": [P, I, I, I, I, I, P, L],
-    "qpg_conv16_f32": [P, I, I, I, I, P, I, P, I, I, I, I, I, I, I, I, I, P, I, I, P, P],
-    "qpg_tpack_f32": [P, I, I, I, I, P],
-    "qpg_resblock_f32": [P, I, I, I, P, P, P, P, P],
-    "qpg_pose_to_euler_f64": [P, L, I, P, P, P, P, P, I, P, P],
-    "qpg_pae_phase_f32": [P, P, P, P, P, I, L, L, L, P, L, P, P, P],
-    "qpg_pae_train_ws_floats": [I, P],
-    "qpg_pae_train_forward_f32": [P, P, P, L, P, I, I, P, L, P],
-    "qpg_pae_train_backward_f32": [P, I, P, L, P],
-    "qpg_pae_adamw_f32": [P, P, P, P, L, c_double, c_double, c_double, c_double, c_double, L],
-    "qpg_vq_argmin_f32": [P, P, P, L, I, I, P, P, P],
-    "qpg_vq_gather_f32": [P, P, L, I, I, P, P],
-    "qpg_vq_encode_f32": [P, P, I, I, P, L, P, P, P],
-    "qpg_vq_decode_f32": [P, P, I, I, P, L, P, P],
-    "qpg_vq_loss_f32": [P, P, I, I, I, P, c_float, c_float, c_float, c_float, P, L, P],
-    "qpg_vq_loss_grad_f32": [P, P, I, I, I, c_float, c_float, c_float, c_float, P],
-    "qpg_vq_latent_stats_f32": [P, P, P, L, I, P, L, P],
-    "qpg_vq_commit_grad_f32": [P, P, L, I, c_float, P, P],
-    "qpg_vq_code_sums_f32": [P, P, L, I, I, P, P, P, L],
-    "qpg_vq_ema_update_f32": [P, P, P, P, P, P, c_float, c_float, I, I, P, I, P, P, L, P],
-    "qpg_vq_code_norms_f32": [P, I, I, P],
-    "qpg_conv1d_bwd_data_f32": [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P, L],
-    "qpg_conv1d_bwd_weight_f32": [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, L],
-    "qpg_adam_step_f32": [P, P, P, P, L, c_float, c_float, c_float, c_float, L],
-    "qpg_comm_allgather": [P, P, P, L],
-    "qpg_comm_alltoall": [P, P, P, L],
-    "qpg_comm_allreduce_max_i32": [P, P, L],
-    "qpg_allreduce_min_u64": [P, P, L],
-    "qpg_pack_min_u64": [P, P, L, P],
-    "qpg_unpack_min_u64": [P, L, c_float, P, P],
-    "qpg_match_steps": [P, P, P, P, P, P, P, I, P, P, I, P, P, I, P, I, I, I, I, I, I, P, P, P, P, P, P, P],
-    "qpg_match_steps_batch": [P, P, P, P, P, P, P, I, P, P, I, P, P, I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, L, P],
-    "qpg_fuse_best_ranked": [P, P, P, P, I, I, P],
-}
+# The binding is derived from include/qpg.h: the header is the one place that states a prototype or a constant.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_HOOKS_RE = re.compile(r"#ifdef QPG_DEBUG_HOOKS\n(.*?)#endif", re.S)
+_PROTO_RE = re.compile(r"\s*([\w\s*]+?)\s*\b(qpg_\w+)\s*\(([^()]*)\)\s*")
+# on_stream: the entry point starts (qpg_ctx*, void* stream, ...) - the ones call() / prepare() launch; hook: it sits in
+# the #ifdef QPG_DEBUG_HOOKS block (experiment builds only, the product library does not export it)
+Prototype = collections.namedtuple("Prototype", "restype argtypes on_stream hook")
 
 
-QPG_VQ_MAX_DOWN, QPG_VQ_MAX_DEPTH = 4, 4
+def _ctype(decl, name, ret=False):
+    """ctypes type of one C parameter or return type.  Any pointer is a c_void_p (it accepts byref(), string buffers, None,
+    integers and c_void_p handles; a returned char* is a c_char_p), a scalar goes by its type word.  A word _SCALARS does
+    not know raises with the function's name: guessing `int` would corrupt the call silently."""
+    words = [w for w in decl.replace("*", " ").split() if w != "const"]
+    if "*" in decl:
+        return ctypes.c_char_p if ret and words[0] == "char" else c_void_p
+    if ret and words == ["void"]:
+        return None
+    if not words or words[0] not in _SCALARS:
+        raise TypeError("%s: no ctypes mapping for %r" % (name, " ".join(decl.split())))
+    return _SCALARS[words[0]]
+
+
+def _number(text):
+    text = text.strip()
+    while text.startswith("(") and text.endswith(")"):
+        text = text[1:-1].strip()
+    m = re.fullmatch(r"(\d+)\s*<<\s*(\d+)", text)
+    if m:
+        return int(m.group(1)) << int(m.group(2))
+    try:
+        return int(text, 0)
+    except ValueError:
+        return float(text)
+
+
+def parse_header(path=HEADER_PATH):
+    """One pass over the header: ({function name: Prototype}, {QPG_* constant: int or float})."""
+    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    consts = {m.group(1): _number(m.group(2)) for m in re.finditer(r"^#define[ \t]+(QPG_\w+)[ \t]+(\S.*)$", txt, re.M)}
+    protos = {}
+    for hook, body in [(False, _HOOKS_RE.sub("", txt))] + [(True, blk) for blk in _HOOKS_RE.findall(txt)]:
+        body = re.sub(r'^[ \t]*(#.*|extern "C" \{)$', "", body, flags=re.M)
+        for stmt in body.split(";"):
+            if "(" not in stmt:
+                continue                                 # (typedefs, struct members)
+            m = _PROTO_RE.fullmatch(stmt)
+            if not m:
+                raise TypeError("%s: not a prototype: %r" % (path, " ".join(stmt.split())))
+            ret, name, params = m.groups()
+            params = [] if params.strip() in ("", "void") else params.split(",")
+            on_stream = len(params) > 1 and "qpg_ctx" in params[0] and params[1].split() == ["void*", "stream"]
+            protos[name] = Prototype(_ctype(ret, name, ret=True), [_ctype(p, name) for p in params], on_stream, hook)
+    return protos, consts
+
+
+_PROTOS, CONSTANTS = parse_header()
+globals().update(CONSTANTS)              # every `#define QPG_X <number>` of the header is _lib.QPG_X
+
+
+def prototypes():
+    """{name: Prototype} of every function include/qpg.h declares (what load() binds)."""
+    return _PROTOS
+
+
+def declared_symbols():
+    """Every function name include/qpg.h declares for the PRODUCT library (used by the CPU symbol-export test); the
+    #ifdef QPG_DEBUG_HOOKS block - experiment builds only - is debug_hook_symbols()."""
+    return sorted(n for n, p in _PROTOS.items() if not p.hook)
+
+
+def debug_hook_symbols():
+    return sorted(n for n, p in _PROTOS.items() if p.hook)
 
 
 class ConvDesc(ctypes.Structure):
@@ -143,24 +117,6 @@ class VqModel(ctypes.Structure):
                 ("dec_res_pack", (c_void_p * QPG_VQ_MAX_DEPTH) * QPG_VQ_MAX_DOWN)]
 
 
-_HOOKS_RE = re.compile(r"#ifdef QPG_DEBUG_HOOKS\n(.*?)#endif", re.S)
-
-
-def declared_symbols():
-    """Every function name include/qpg.h declares for the PRODUCT library (used by the CPU symbol-export test); the
-    #ifdef QPG_DEBUG_HOOKS block - experiment builds only - is debug_hook_symbols()."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    txt = _HOOKS_RE.sub("", txt)
-    return sorted(set(re.findall(r"\b(qpg_[a-z0-9_]+)\s*\(", txt)))
-
-
-def debug_hook_symbols():
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(n for blk in _HOOKS_RE.findall(txt) for n in re.findall(r"\b(qpg_[a-z0-9_]+)\s*\(", blk)))
-
-
 def load():
     """dlopen the library (works without a GPU: symbols only)."""
     global _lib
@@ -178,63 +134,14 @@ def load():
         if _build.lib_build_id(LIB_PATH) != want:
             _build.build_lib(verbose=False)
     lib = ctypes.CDLL(LIB_PATH)
-    lib.qpg_version.restype = c_int
-    lib.qpg_build_id.restype = ctypes.c_char_p
-    lib.qpg_build_id.argtypes = []
-    lib.qpg_ctx_set_option.argtypes = [c_void_p, c_int, c_int]
-    lib.qpg_ctx_get_option.argtypes = [c_void_p, c_int, ctypes.POINTER(c_int)]
-    lib.qpg_ctx_create.argtypes = [c_int, ctypes.POINTER(c_void_p)]
-    lib.qpg_ctx_create.restype = c_int
-    lib.qpg_ctx_destroy.argtypes = [c_void_p]
-    lib.qpg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-    lib.qpg_vq_workspace_floats.argtypes = [c_void_p, c_int, c_int]
-    lib.qpg_vq_workspace_floats.restype = c_int64
-    lib.qpg_conv1d_wgrad_ws_floats.argtypes = [c_int, c_int, c_int, c_int]
-    lib.qpg_conv1d_wgrad_ws_floats.restype = c_int64
-    lib.qpg_vq_code_sums_ws_bytes.argtypes = [c_int64, c_int, c_int]
-    lib.qpg_vq_code_sums_ws_bytes.restype = c_int64
-    lib.qpg_text_percode_ws_bytes.argtypes = [c_int64, c_int, c_int, c_int]
-    lib.qpg_text_percode_ws_bytes.restype = c_int64
-    lib.qpg_percode_select_mixed_ws_bytes.argtypes = [c_int, c_int]
-    lib.qpg_percode_select_mixed_ws_bytes.restype = c_int64
-    lib.qpg_percode_select_mixed_ws_stride.argtypes = [c_int]
-    lib.qpg_percode_select_mixed_ws_stride.restype = c_int64
-    lib.qpg_merge_mixed_ws_bytes.argtypes = [c_int, c_int, c_int]
-    lib.qpg_audio_hl_supported.argtypes = [c_int] * 6
-    lib.qpg_audio_hl1_supported.argtypes = [c_int] * 6
-    lib.qpg_audio_hl1_db_bytes.argtypes = [c_int, c_int]
-    lib.qpg_audio_hl1_db_bytes.restype = c_int64
-    lib.qpg_audio_hl_db_bytes.argtypes = [c_int, c_int]
-    lib.qpg_audio_hl_db_bytes.restype = c_int64
-    lib.qpg_audio_hl_query_bytes.argtypes = [c_int, c_int]
-    lib.qpg_audio_hl_query_bytes.restype = c_int64
-    lib.qpg_hl_rows_bytes.argtypes = [c_int64, c_int]
-    lib.qpg_hl_rows_bytes.restype = c_int64
-    lib.qpg_hl_cols_bytes.argtypes = [c_int, c_int]
-    lib.qpg_hl_cols_bytes.restype = c_int64
-    lib.qpg_percode_select_exact_ws_bytes.argtypes = [c_int, c_int64, c_int]
-    lib.qpg_percode_select_exact_ws_bytes.restype = c_int64
-    lib.qpg_merge_mixed_ws_bytes.restype = c_int64
-    lib.qpg_conv16_image_bytes.argtypes = [c_int, c_int, c_int]
-    lib.qpg_conv16_image_bytes.restype = c_int64
-    lib.qpg_comm_unique_id.argtypes = [ctypes.c_char_p, c_int64]
-    lib.qpg_comm_create.argtypes = [c_void_p, ctypes.c_char_p, c_int64, c_int, c_int, ctypes.POINTER(c_void_p)]
-    lib.qpg_comm_destroy.argtypes = [c_void_p]
-    for name, at in (("qpg_debug_convt_shape", [c_int, c_int]), ("qpg_debug_convt_opts", [c_int, c_int]),
-                     ("qpg_debug_gemm64_waves", [c_int])):      # -DQPG_DEBUG_HOOKS variant libraries only (QPG_LIB_PATH)
-        if hasattr(lib, name):
-            getattr(lib, name).argtypes = at
-    lib.qpg_vq_reduce_ws_bytes.argtypes = []
-    lib.qpg_vq_reduce_ws_bytes.restype = c_int64
-    for name, sig in _SIGS.items():
+    for name, proto in _PROTOS.items():
+        if proto.hook and not hasattr(lib, name):
+            continue                                     # (-DQPG_DEBUG_HOOKS variant libraries only: QPG_LIB_PATH)
         fn = getattr(lib, name)
-        fn.argtypes = [c_void_p, c_void_p] + sig
-        fn.restype = c_int
+        fn.argtypes, fn.restype = proto.argtypes, proto.restype
     _lib = lib
     return lib
 
-
-QPG_OPT_GATE_DEDUP_FROM_CHAINS = 0
 
 
 def set_option(device, option, value):
@@ -286,6 +193,20 @@ def _raw_stream(idx):
     return torch.cuda.current_stream(idx).cuda_stream
 
 
+def _convert(args):
+    """What the foreign call receives: tensors as their data_ptr() integers, structures by reference."""
+    conv = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            if not (a.is_cuda and a.is_contiguous()):
+                raise AssertionError("device-resident contiguous tensor required")
+            conv.append(a.data_ptr())
+        elif isinstance(a, ctypes.Structure):
+            conv.append(ctypes.byref(a))
+        else:
+            conv.append(a)                      # (ints, floats, None, c_void_p handles)
+    return conv
+
 
 def call(name, device, *args):
     """Invoke a C-ABI entry point on torch's current stream of `device`; raise on error.
@@ -308,16 +229,7 @@ def call(name, device, *args):
             return call(name, device, *args)
     n_calls += 1
     stream = _raw_stream(idx)
-    conv = []
-    for a in args:
-        if isinstance(a, torch.Tensor):
-            if not (a.is_cuda and a.is_contiguous()):
-                raise AssertionError("device-resident contiguous tensor required")
-            conv.append(a.data_ptr())
-        elif isinstance(a, ctypes.Structure):
-            conv.append(ctypes.byref(a))
-        else:
-            conv.append(a)                      # (ints, floats, None, c_void_p handles)
+    conv = _convert(args)
     h = _ctx.get(idx)
     if h is None:
         h = ctx(device)
@@ -335,16 +247,7 @@ def prepare(name, device, *args):
     if idx is None or idx != _get_device():
         return lambda: call(name, device, *args)
     stream = _raw_stream(idx)
-    conv = []
-    for a in args:
-        if isinstance(a, torch.Tensor):
-            if not (a.is_cuda and a.is_contiguous()):
-                raise AssertionError("device-resident contiguous tensor required")
-            conv.append(a.data_ptr())
-        elif isinstance(a, ctypes.Structure):
-            conv.append(ctypes.byref(a))
-        else:
-            conv.append(a)
+    conv = _convert(args)
     h = _ctx.get(idx)
     if h is None:
         h = ctx(device)

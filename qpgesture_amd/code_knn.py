@@ -21,15 +21,15 @@ import ctypes
 from .constant import (ABSENT_DIST, NUM_AUDIO_FEAT_FRAMES, STEP_SZ, WAVVQ_GROUP_SIZE, codebook_size, num_frames,
                        num_frames_code)
 
-MODE_AUD_TXT, MODE_AUD, MODE_TXT = 0, 1, 2
+MODE_AUD_TXT, MODE_AUD, MODE_TXT = _lib.QPG_MODE_AUD_TXT, _lib.QPG_MODE_AUD, _lib.QPG_MODE_TXT
 # mixed-precision audio sweep: a-priori error bound of qpg_audio_cosine_mx (QPG_AUDIO_MX_ERR of include/qpg.h) and the
 # band inside which qpg_percode_select_mixed_f64 re-evaluates (two values further apart than 2 x the bound are ordered
 # like the exact distances; 5 % margin on top)
-AUDIO_MX_ERR = 2.05e-6
+AUDIO_MX_ERR = _lib.QPG_AUDIO_MX_ERR
 AUDIO_MX_BAND = 2.1 * AUDIO_MX_ERR
 # the split-operand f16 sweep (qpg_audio_cosine_hl, QPG_AUDIO_HL_ERR): a tighter bound, a narrower band.  (Round 4's
 # 32-row kernel runs the cross products through the h h' chains, cross terms first: the same budget, csrc/qpg_audio_hl.hip.)
-AUDIO_HL_ERR = 1.3e-6
+AUDIO_HL_ERR = _lib.QPG_AUDIO_HL_ERR
 AUDIO_HL_BAND = 2.1 * AUDIO_HL_ERR
 
 # bits of the trouble word the sweeps / selects raise (stats[1] of include/qpg.h) and the walk carries out with the codes
@@ -1153,7 +1153,7 @@ class CodeKNN:
                     M > 0 and not self.serial_walk)
         if not prefused:
             gate = torch.empty((3, max(CL * M, 1) * steps, db.K), dtype=torch.int32, device=dev)
-        mode_w = mode | (0x200 if prefused else 0)             # QPG_MODE_PREFUSED
+        mode_w = mode | (_lib.QPG_MODE_PREFUSED if prefused else 0)
 
         def sl(t):
             return None if t is None else t[q0:q0 + CL * M * steps]
@@ -1167,8 +1167,8 @@ class CodeKNN:
         else:
             _lib.call("qpg_match_steps", dev, sl(T["aud_rank"]), sl(T["aud_idx"]), sl(T["txt_rank"]), sl(T["txt_idx"]),
                       db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G,
-                      db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp, mode_w | (0x100 if self.serial_walk else 0), M,
-                      steps, db.K, int(seed_code), sp,
+                      db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp,
+                      mode_w | (_lib.QPG_MODE_SERIAL_WALK if self.serial_walk else 0), M, steps, db.K, int(seed_code), sp,
                       gate, out_codes, out_phase, out_vote, status, self._guard_stats[1:2])
         if out_pin is not None:
             return out_codes, out_phase, out_vote, status
@@ -1221,8 +1221,8 @@ class CodeKNN:
             return None if t is None else t[:Qt]
         _lib.call("qpg_match_steps_batch", dev, sl(T["aud_rank"]), sl(T["aud_idx"]), sl(T["txt_rank"]), sl(T["txt_idx"]),
                   db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G,
-                  db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp, mode | (0x200 if prefused else 0), M, steps, db.K, CL,
-                  sc, sp, gate, codes_d, out_phase, votes_d, status_d, 2, self._guard_stats[1:2])
+                  db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp, mode | (_lib.QPG_MODE_PREFUSED if prefused else 0), M,
+                  steps, db.K, CL, sc, sp, gate, codes_d, out_phase, votes_d, status_d, 2, self._guard_stats[1:2])
         self._last_ints = torch.cat((codes_d.view(CL, n_c), votes_d.view(CL, n_v), status_d), dim=1)
         self._last_gate_tables = gate                       # (tests compare the candidate tables of the two fusion paths)
         return codes_d, out_phase, votes_d

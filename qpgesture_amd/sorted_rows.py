@@ -10,7 +10,7 @@ import torch
 from . import _lib
 
 U32 = 2.0 ** -24
-HL_GEMM_ERR = 1.3e-6          # QPG_AUDIO_HL_ERR: the split-f16 GEMM on unit-norm operands, f64 block sums (round 3's kernel)
+HL_GEMM_ERR = _lib.QPG_AUDIO_HL_ERR          # the split-f16 GEMM on unit-norm operands, f64 block sums (round 3's kernel)
 
 
 def gemm32_err(d):

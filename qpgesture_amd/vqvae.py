@@ -322,7 +322,7 @@ class VQVAE:
     # split-operand f16 convolutions (round 5, csrc/qpg_conv16.hip): the same layers at ~3/16 of the f32 matrix time per
     # flop, agreeing with the f32 kernels to ~1e-5 - NOT bit-identical, so they serve under a margin check (encode below)
     # ------------------------------------------------------------------------------------------
-    WEXP_FROM_IMAGE = 0x7fff          # QPG_CONV16_WEXP_FROM_IMAGE: the kernel reads the scale exponent from the image
+    WEXP_FROM_IMAGE = _lib.QPG_CONV16_WEXP_FROM_IMAGE          # the kernel reads the scale exponent from the image
 
     def _conv16_image(self, c, read_exp=True):
         """(image, scale exponent) of convolution c for qpg_conv16_f32; built on first use, dropped when the weights change.

@@ -23,18 +23,40 @@ def test_library_loads_and_exports_every_declared_symbol():
 
 
 def test_bindings_cover_the_header():
-    declared = set(_lib.declared_symbols())
-    bound = set(_lib._SIGS) | {"qpg_version", "qpg_ctx_create", "qpg_ctx_destroy", "qpg_last_error",
-                               "qpg_vq_workspace_floats", "qpg_vq_reduce_ws_bytes",
-                               "qpg_conv1d_wgrad_ws_floats", "qpg_vq_code_sums_ws_bytes",
-                               "qpg_text_percode_ws_bytes", "qpg_percode_select_mixed_ws_bytes",
-                               "qpg_percode_select_mixed_ws_stride",
-                               "qpg_merge_mixed_ws_bytes", "qpg_build_id", "qpg_ctx_set_option", "qpg_ctx_get_option",
-                               "qpg_percode_select_exact_ws_bytes", "qpg_audio_hl_supported",
-                               "qpg_audio_hl_db_bytes", "qpg_audio_hl_query_bytes", "qpg_hl_rows_bytes",
-                               "qpg_hl_cols_bytes", "qpg_dev_kernarg", "qpg_audio_hl1_supported", "qpg_audio_hl1_db_bytes",
-                               "qpg_conv16_image_bytes", "qpg_comm_unique_id", "qpg_comm_create", "qpg_comm_destroy"}
-    assert declared == bound
+    """load() leaves no declared function at ctypes' defaults: each carries the argtypes and restype the header parser
+    derived, and every launch - (qpg_ctx*, void* stream, ...) - returns int."""
+    lib, protos = _lib.load(), _lib.prototypes()
+    assert set(_lib.declared_symbols()) | set(_lib.debug_hook_symbols()) == set(protos)
+    assert not set(_lib.declared_symbols()) & set(_lib.debug_hook_symbols())
+    launches = 0
+    for name in _lib.declared_symbols():
+        fn, proto = getattr(lib, name), protos[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == proto.argtypes, name
+        assert fn.restype is proto.restype, name
+        if proto.on_stream:
+            assert fn.restype is ctypes.c_int and list(fn.argtypes[:2]) == [ctypes.c_void_p] * 2, name
+            launches += 1
+    assert launches >= 88 and protos["qpg_audio_cosine_f64"].on_stream and not protos["qpg_ctx_create"].on_stream
+
+
+def test_pinned_prototypes():
+    """Six prototypes written out as literals, one per shape the header -> ctypes mapping has to get right (a parser bug
+    that is also a bug of the tests around it can not hide behind these)."""
+    lib = _lib.load()
+    P, I, L, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+    want = {
+        "qpg_audio_cosine_f64": (I, [P, P, P, I, I, I, P, I, I, I, P, P, P, I, P, L]),
+        "qpg_percode_select_mixed_f64_cut": (I, [P, P, P, I, L, I, P, L, I, D, ctypes.c_int32, P, P, P, I, L, P, I, I, P, I, I,
+                                                 I, P, P, P, D, D, P, P, L, I, P, P, I, I]),
+        "qpg_hl_rows_bytes": (L, [L, I]),                       # int64_t return and parameter
+        "qpg_last_error": (I, [P, ctypes.c_size_t]),            # size_t
+        "qpg_ctx_create": (I, [I, P]),                          # pointer to pointer
+        "qpg_build_id": (ctypes.c_char_p, []),                  # const char*, no parameters
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert ctypes.sizeof(L) == 8 and ctypes.sizeof(I) == 4 and ctypes.sizeof(ctypes.c_size_t) == 8
 
 
 def test_product_library_exports_no_debug_hooks_and_is_built_from_this_tree():
@@ -191,38 +213,148 @@ def test_oracle_forward_loss_terms():
     assert abs(float(loss) - want) < 1e-6
 
 
+def _clang(*args):
+    """The compiler the tree is built with, on C input, syntax only (it has to exist: nothing here builds without it)."""
+    import subprocess
+    from qpgesture_amd import build
+    clang = subprocess.check_output([build.HIPCC, "-print-prog-name=clang"]).decode().strip()
+    return subprocess.check_output([clang, "-x", "c", "-fsyntax-only", "-I", os.path.dirname(_lib.HEADER_PATH)]
+                                   + list(args)).decode()
+
+
+def _compiler_view():
+    """include/qpg.h as clang's AST states it: {function: (return kind, [parameter kinds], on_stream)} over the product
+    declarations and the -DQPG_DEBUG_HOOKS ones, the set of names only the latter has, and {struct typedef: field names}.
+    Kinds: ptr / i32 / i64 / f32 / f64 / size_t, and cstr (a returned char*) / void for return types - typedef names are
+    resolved through the AST's own typedef declarations, not by their spelling."""
+    import json
+    funcs, names, records = {}, [], {}
+    for flags in ([], ["-DQPG_DEBUG_HOOKS"]):
+        top = json.loads(_clang("-Xclang", "-ast-dump=json", *flags, _lib.HEADER_PATH))["inner"]
+        typedefs = {n["name"]: n["type"].get("desugaredQualType", n["type"]["qualType"])
+                    for n in top if n["kind"] == "TypedefDecl"}
+
+        def kind(t, ret=False):
+            t = t.strip()
+            if t.endswith("*"):
+                return "cstr" if ret and t.replace("const", "").replace(" ", "") == "char*" else "ptr"
+            t = t.replace("const ", "")
+            while t in typedefs:
+                t = typedefs[t]
+            return {"int": "i32", "long": "i64", "long long": "i64", "unsigned long": "size_t", "float": "f32",
+                    "double": "f64", "void": "void"}[t]
+        last_record = None
+        for n in top:
+            if n["kind"] == "RecordDecl":
+                last_record = [f["name"] for f in n.get("inner", []) if f["kind"] == "FieldDecl"]
+            elif n["kind"] == "TypedefDecl" and n["name"].startswith("qpg_") and last_record:
+                records[n["name"]] = last_record             # (typedef struct { ... } qpg_x;)
+            elif n["kind"] == "FunctionDecl" and n["name"].startswith("qpg_"):
+                params = [(p["type"]["qualType"], p.get("name")) for p in n.get("inner", []) if p["kind"] == "ParmVarDecl"]
+                on_stream = len(params) > 1 and params[0][0] == "qpg_ctx *" and params[1] == ("void *", "stream")
+                ret = n["type"]["qualType"].split("(")[0]
+                funcs[n["name"]] = (kind(ret, ret=True), [kind(t) for t, _ in params], on_stream)
+        names.append({n["name"] for n in top if n["kind"] == "FunctionDecl" and n["name"].startswith("qpg_")})
+    return funcs, names[1] - names[0], records
+
+
+_CTYPES_KIND = {ctypes.c_void_p: "ptr", ctypes.c_int: "i32", ctypes.c_int64: "i64", ctypes.c_float: "f32",
+                ctypes.c_double: "f64", ctypes.c_size_t: "size_t", ctypes.c_char_p: "cstr", None: "void"}
+
+
+def _signature_mismatches(bound, funcs):
+    """bound: {name: (restype, argtypes)} as ctypes types; funcs: _compiler_view()[0].  One line per function that differs."""
+    bad = ["%s: bound but not declared" % n for n in sorted(set(bound) - set(funcs))]
+    bad += ["%s: declared but not bound" % n for n in sorted(set(funcs) - set(bound))]
+    for name in sorted(set(bound) & set(funcs)):
+        restype, argtypes = bound[name]
+        got = (_CTYPES_KIND[restype], None if argtypes is None else [_CTYPES_KIND[t] for t in argtypes])
+        if got != funcs[name][:2]:
+            bad.append("%s: bound as %s, the compiler says %s" % (name, got, funcs[name][:2]))
+    return bad
+
+
 def test_ctypes_signatures_match_the_header():
-    """Every binding in qpgesture_amd/_lib._SIGS has the argument count and the pointer / integer / float kinds of
-    its prototype in include/qpg.h (a drifted ctypes signature would corrupt the call silently)."""
-    import ctypes
+    """What load() has set on the library agrees with the COMPILER's reading of include/qpg.h (clang's AST, with and without
+    -DQPG_DEBUG_HOOKS), for every declared function: arity, the kind of every parameter and the kind of the return value
+    (a drifted ctypes signature would corrupt the call silently).  The hook functions, which the product library does not
+    export, are held against the parser's output instead."""
+    lib, protos = _lib.load(), _lib.prototypes()
+    funcs, hooks, _ = _compiler_view()
+    assert hooks == set(_lib.debug_hook_symbols()) and set(funcs) - hooks == set(_lib.declared_symbols())
+    bound = {}
+    for name, proto in protos.items():
+        fn = proto if proto.hook else getattr(lib, name)
+        bound[name] = (fn.restype, fn.argtypes)
+    assert len(bound) >= 120
+    assert _signature_mismatches(bound, funcs) == []
+    assert {n for n, p in protos.items() if p.on_stream} == {n for n, f in funcs.items() if f[2]}
+
+
+def _scratch_header(tmp_path, *edits):
+    txt = open(_lib.HEADER_PATH).read()
+    for old, new in edits:
+        assert txt.count(old) == 1, old
+        txt = txt.replace(old, new)
+    path = str(tmp_path / "qpg.h")
+    with open(path, "w") as f:
+        f.write(txt)
+    return path
+
+
+def test_signature_check_catches_planted_errors(tmp_path):
+    """The comparison above is not vacuous: a header copy with one int64_t parameter turned into int and one return type
+    changed, given to the parser while the compiler reads the real header, is reported - those two functions, nothing else."""
+    path = _scratch_header(tmp_path, ("int64_t qpg_hl_rows_bytes(int64_t R, int D);", "int64_t qpg_hl_rows_bytes(int R, int D);"),
+                           ("int64_t qpg_vq_reduce_ws_bytes(void);", "int qpg_vq_reduce_ws_bytes(void);"))
+    protos, _ = _lib.parse_header(path)
+    bad = _signature_mismatches({n: (p.restype, p.argtypes) for n, p in protos.items()}, _compiler_view()[0])
+    print("\n".join(bad))
+    assert len(bad) == 2 and bad[0].startswith("qpg_hl_rows_bytes: ") and bad[1].startswith("qpg_vq_reduce_ws_bytes: ")
+
+
+def test_parser_refuses_an_unknown_type_word(tmp_path):
+    """A type the mapping does not know is an error that names the function - never a silent `int`."""
+    for old, new in (("int64_t qpg_hl_rows_bytes(int64_t R, int D);", "int64_t qpg_hl_rows_bytes(uint64_t R, int D);"),
+                     ("int64_t qpg_hl_rows_bytes(int64_t R, int D);", "long qpg_hl_rows_bytes(int64_t R, int D);"),
+                     ("int64_t qpg_hl_rows_bytes(int64_t R, int D);", "int64_t qpg_hl_rows_bytes(int64_t R, void D);")):
+        with pytest.raises(TypeError, match="qpg_hl_rows_bytes"):
+            _lib.parse_header(_scratch_header(tmp_path, (old, new)))
+
+
+def test_struct_mirrors_have_the_compiler_s_layout(tmp_path):
+    """ConvDesc / VqModel are hand-written mirrors of qpg_conv_desc / qpg_vq_model: size, field names, field order and every
+    field offset are the compiler's (clang's record layouts of the header's own typedefs)."""
     import re
-    hdr = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(?:int|int64_t|void)\s+(qpg_\w+)\s*\(([^;{]*?)\)\s*;", hdr, flags=re.S):
-        protos[m.group(1)] = [re.sub(r"\s+", " ", a.strip()) for a in m.group(2).split(",")]
+    src = str(tmp_path / "layout.c")
+    with open(src, "w") as f:
+        f.write('#include "qpg.h"\nint use[sizeof(qpg_conv_desc) + sizeof(qpg_vq_model)];\n')
+    dump = _clang("-Xclang", "-fdump-record-layouts-simple", src)
+    layouts = {m.group(1): (int(m.group(2)), [int(o) for o in m.group(3).split(",")]) for m in re.finditer(
+        r"Type: (\w+)\n\nLayout: <ASTRecordLayout\n\s*Size:(\d+)\n.*?FieldOffsets: \[([\d, ]+)\]>", dump, re.S)}
+    fields = _compiler_view()[2]
+    for cname, mirror in (("qpg_conv_desc", _lib.ConvDesc), ("qpg_vq_model", _lib.VqModel)):
+        bits, offsets = layouts[cname]
+        assert [n for n, _ in mirror._fields_] == fields[cname], cname
+        assert ctypes.sizeof(mirror) * 8 == bits, cname
+        assert [getattr(mirror, n).offset * 8 for n, _ in mirror._fields_] == offsets, cname
+    assert ctypes.sizeof(_lib.ConvDesc) == 48 and ctypes.sizeof(_lib.VqModel) == 4144
+    assert [getattr(_lib.ConvDesc, n).offset for n, _ in _lib.ConvDesc._fields_] == [0, 8, 16, 20, 24, 28, 32, 40]
 
-    def kind_of_c(arg):
-        if "*" in arg:
-            return "ptr"
-        t = arg.split()[0] if " " in arg else arg
-        if t in ("float",):
-            return "f32"
-        if t in ("double",):
-            return "f64"
-        if t in ("int64_t",):
-            return "i64"
-        return "i32"                                  # int, int32_t
 
-    def kind_of_ct(t):
-        if t is ctypes.c_void_p:
-            return "ptr"
-        return {ctypes.c_float: "f32", ctypes.c_double: "f64", ctypes.c_int64: "i64"}.get(t, "i32")
-    for name, sig in _lib._SIGS.items():
-        args = protos[name]
-        assert [kind_of_c(a) for a in args[:2]] == ["ptr", "ptr"], name          # qpg_ctx*, void* stream
-        want = [kind_of_c(a) for a in args[2:]]
-        got = [kind_of_ct(t) for t in sig]
-        assert got == want, (name, got, want)
+def test_header_constants_equal_the_literals_they_replaced():
+    from qpgesture_amd import code_knn, sorted_rows, vqvae
+    assert _lib.QPG_MODE_PREFUSED == 0x200 and _lib.QPG_MODE_SERIAL_WALK == 0x100
+    assert (code_knn.MODE_AUD_TXT, code_knn.MODE_AUD, code_knn.MODE_TXT) == (0, 1, 2)
+    assert _lib.QPG_CONV16_WEXP_FROM_IMAGE == 0x7fff == vqvae.VQVAE.WEXP_FROM_IMAGE
+    assert _lib.QPG_VQ_MAX_DOWN == 4 and _lib.QPG_VQ_MAX_DEPTH == 4
+    assert _lib.QPG_OPT_GATE_DEDUP_FROM_CHAINS == 0
+    assert code_knn.AUDIO_MX_ERR == _lib.QPG_AUDIO_MX_ERR == 2.05e-6
+    assert code_knn.AUDIO_HL_ERR == sorted_rows.HL_GEMM_ERR == _lib.QPG_AUDIO_HL_ERR == 1.3e-6
+    # the other shapes a value takes in the header: parenthesised, negative, a shift; integers stay integers
+    assert _lib.QPG_EINVAL == -1 and _lib.QPG_PAE_MAX_CHUNK == 1 << 22 and _lib.CONSTANTS["QPG_PAET_PARAM_FLOATS"] == 1034098
+    assert all(type(v) in (int, float) for v in _lib.CONSTANTS.values()) and type(_lib.QPG_PAE_MAX_CHUNK) is int
+    assert "QPG_H" not in _lib.CONSTANTS
 
 
 # ---------------------------------------------------------------------------------------------------------------

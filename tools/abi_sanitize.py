@@ -29,8 +29,10 @@ def child():
     n_calls = n_refused = 0
     patterns = [lambda t: 0, lambda t: -1, lambda t: (1 << 30)]
     for ctx in ctxs:
-        for name, sig in sorted(_lib._SIGS.items()):
-            fn = getattr(lib, name)
+        for name, proto in sorted(_lib.prototypes().items()):
+            if not proto.on_stream:
+                continue
+            fn, sig = getattr(lib, name), proto.argtypes[2:]
             for pat in patterns:
                 args = []
                 for t in sig:
