@@ -8,7 +8,9 @@ Design difference from the reference (same results): the audio and text scans de
 the query position, never on the running (code, phase) state, so all Q = 8*M scans of a clip are
 issued as two batched sweeps, and the sequential part walks (Q,512) tables on the device.
 """
-import time
+import ctypes
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -16,7 +18,6 @@ import torch
 from . import _lib
 from .parallel import allreduce_max_, allreduce_min_index, exchange_bytes, shard_rows
 from .sorted_rows import SortedRows
-import ctypes
 
 from .constant import (ABSENT_DIST, NUM_AUDIO_FEAT_FRAMES, STEP_SZ, WAVVQ_GROUP_SIZE, codebook_size, num_frames,
                        num_frames_code)
@@ -360,6 +361,110 @@ class GestureDB:
         return self.lo
 
 
+# ----------------------------------------------------------------------------------------------
+# the plan of a sweep / of a step: which kernels, in which order.  Pure functions of plain values (no torch, no library):
+# CodeKNN computes a plan once per call and its methods carry it out; the decisions are tested on the CPU
+# ----------------------------------------------------------------------------------------------
+# the switches of a CodeKNN that a plan reads (documented where CodeKNN.__init__ sets them; the defaults are its own)
+Knobs = namedtuple("Knobs", "audio_precision audio_kernel text_kernel tie_eps mixed_single_launch sharded_mixed "
+                   "sharded_mixed_min_gflop force_sharded overlap_sweeps text_after_sweep audio_first fused_pack rank_cut "
+                   "split_fuse split_fuse_max_steps host_ranks use_wavvq",
+                   defaults=("mixed", "hl", "mfma", 1e-12, False, True, 20.0, False, True, True, None, True, True, True,
+                             256, False, False))
+# what a plan needs to know about a GestureDB
+DBFacts = namedtuple("DBFacts", "n_local N world K Ga F Dt feature_dtype hl_bound_ok has_hl_image has_txt_sorted hl_planes",
+                     defaults=("f32", True, True, True, 2))
+
+
+class AudioPlan(NamedTuple):
+    path: str           # the select that settles the sweep's matrix: "mixed" | "exact" | "guarded" | "plain"
+    kernel: str         # the sweep kernel qpg_audio_cosine_<kernel>: "hl" | "hl1" | "mx" | "mx_h" | "f64" | "f64_h"
+    band: float         # what the mixed select / merge re-evaluates: AUDIO_HL_BAND / AUDIO_MX_BAND (0: not mixed)
+    cut_top_n: int      # walk-relevance cut of the mixed select: 0 = off, 1 (audio + text), 2 (audio only)
+    fused_rank: bool    # the select writes the ranks as well
+
+
+class StepPlan(NamedTuple):
+    audio: Optional[AudioPlan]      # None: no WavLM audio side (MODE_TXT, or the wavvq sweep, which has one path)
+    text: Optional[str]             # "mfma" | "valu"; None: no text side (MODE_AUD)
+    sharded: bool                   # per-shard tables into the exchange layout, merged behind one collective
+    exchange: Optional[str]         # sharded: "all_to_all" (owner blocks) | "all_gather"
+    clip_pack: bool                 # both query packs in one launch (qpg_clip_pack_hl)
+    split_fuse: bool                # each side's half of the rank fusion behind its own select, into the gate tables
+    overlap: bool                   # the text side on the side stream
+    order: Optional[str]            # overlap: "text_first" | "text_after_sweep" | "audio_first"
+
+
+def plan_audio(kn, db, Q, want_rank=False, reduce=True, out_given=False, cut_top_n=0):
+    """The AudioPlan of one WavLM sweep of Q queries (CodeKNN.sweep_audio's arguments; out_given: `out` is not None)."""
+    C = db.n_local * db.Ga
+    fused_rank = want_rank and db.world == 1
+    local_final = fused_rank and reduce and not out_given           # one GPU: this select decides everything
+    shard_part = (db.world > 1 or kn.force_sharded) and not reduce and out_given     # row shard: sweep_tables merges
+    # (the same number on every rank - the largest shard's - so that all ranks take the same path: the mixed merge has
+    # two more collectives than the f64 one)
+    gflop = 2e-9 * Q * (-(-db.N // db.world) * db.Ga) * NUM_AUDIO_FEAT_FRAMES * db.F
+    guard = kn.tie_eps > 0 and C > 0
+    half = db.feature_dtype == "f16"
+    if (kn.audio_precision == "mixed" and guard and db.K <= 512 and db.hl_bound_ok and
+            (local_final or (shard_part and kn.sharded_mixed and gflop >= kn.sharded_mixed_min_gflop))):
+        hl = kn.audio_kernel == "hl" and db.has_hl_image
+        kernel = ("hl" if db.hl_planes == 2 else "hl1") if hl else ("mx_h" if half else "mx")
+        cut = cut_top_n if (cut_top_n in (1, 2) and local_final and not kn.mixed_single_launch) else 0
+        return AudioPlan("mixed", kernel, AUDIO_HL_BAND if hl else AUDIO_MX_BAND, cut, fused_rank)
+    path = "exact" if (kn.audio_precision == "exact" and guard) else ("guarded" if guard else "plain")
+    return AudioPlan(path, "f64_h" if half else "f64", 0.0, 0, fused_rank)
+
+
+def plan_text(kn, db, Q, reduce=True, out_given=False):
+    """ "mfma" (bounded prefilter over the sorted image + exact band evaluation) or "valu" (the exact-order sweep) for one
+    text sweep of Q queries (CodeKNN.sweep_text's arguments)."""
+    mfma = (kn.text_kernel == "mfma" and db.has_txt_sorted and Q > 0 and kn.audio_precision != "exact" and
+            ((not out_given and reduce and db.world == 1) or (out_given and not reduce)))
+    return "mfma" if mfma else "valu"
+
+
+def plan_step(kn, db, M, steps, mode=MODE_AUD_TXT, for_walk=False, owner_blocks=False):
+    """The StepPlan of CodeKNN.sweep_tables over M windows of `steps` matching steps each."""
+    Q = M * steps
+    sharded = db.world > 1 or kn.force_sharded
+    audio = text = None
+    if mode != MODE_TXT and not kn.use_wavvq:
+        cut = 0
+        if for_walk and kn.rank_cut and not sharded and not kn.host_ranks:
+            cut = 1 if mode == MODE_AUD_TXT else 2
+        audio = plan_audio(kn, db, Q, want_rank=not sharded, reduce=not sharded, out_given=sharded, cut_top_n=cut)
+    if mode != MODE_AUD:
+        text = plan_text(kn, db, Q, reduce=not sharded, out_given=sharded)
+    split = (for_walk and mode == MODE_AUD_TXT and not sharded and not kn.host_ranks and kn.split_fuse and
+             db.K % 16 == 0 and db.K <= 4096 and Q <= kn.split_fuse_max_steps)
+    overlap = mode == MODE_AUD_TXT and kn.overlap_sweeps
+    mfma_text = kn.text_kernel == "mfma" and db.has_txt_sorted and kn.audio_precision != "exact"
+    # (the pack is the split-f16 sweep's: it follows the audio plan.  An hl image exists only for Ga > 1, so the plan's
+    # `n_local * Ga > 0` is the `n_local > 0` this decision used to ask on every database that can be built)
+    clip_pack = (overlap and not kn.use_wavvq and mfma_text and audio.kernel in ("hl", "hl1") and db.Dt % 128 == 0 and
+                 kn.fused_pack)
+    audio_first = mfma_text if kn.audio_first is None else bool(kn.audio_first)
+    after = overlap and kn.text_after_sweep and not audio_first and not kn.use_wavvq
+    order = None
+    if overlap:
+        order = "audio_first" if audio_first else ("text_after_sweep" if after else "text_first")
+    exchange = ("all_to_all" if owner_blocks else "all_gather") if sharded else None
+    return StepPlan(audio, text, sharded, exchange, clip_pack, split, overlap, order)
+
+
+# what CodeKNN._sweep_audio leaves: the per-shard (not yet reduced) tables, the sweep's matrix, the packed queries (the
+# sharded merge re-evaluates requested pairs from them) and the AudioPlan that was carried out
+AudioResult = namedtuple("AudioResult", "dist idx rank D q32 qn2 plan")
+
+
+def _grown(buf, nbytes, dev, zero=False):
+    """`buf` if it holds nbytes, else a new byte buffer of that size (zero: zero-filled)."""
+    if buf is not None and buf.numel() >= nbytes:
+        return buf
+    return (torch.zeros if zero else torch.empty)((nbytes,), dtype=torch.uint8, device=dev)
+
+
 class CodeKNN:
     """Mirror of the reference's CodeKNN (GestureKNN.py:422-721) over a GestureDB."""
 
@@ -436,6 +541,30 @@ class CodeKNN:
         # embeddings: silent frames share one vector) get NumPy's unstable-sort order like the reference's.
         self.host_ranks = False
 
+        # state that appears with use: caches per shape / clip length / knobs, the side stream and its events, grown buffers
+        self._qpos, self._qcache, self._layouts, self._mm_cache, self._pinned_ints, self._plans = None, {}, {}, {}, {}, {}
+        self._side_stream = self._side_gate = self._side_done = self._sweep_event = None
+        self._mix_ws = self._exact_ws = self._hl_qimage = None
+        # bench.py: HIP events around the sweep kernel of every kernel_events_every-th call, appended to kernel_events
+        # (a list; None: off), taken from kernel_event_pool while it lasts (events created ahead of the timed region)
+        self.kernel_events, self.kernel_events_every, self.kernel_event_pool, self._ev_calls = None, 1, None, 0
+        # diagnostics of the last sweep / walk: tests, tools and bench.py read them, nothing in the package decides by them
+        self.text_fallbacks, self.tables, self._last_mix_Q = 0, None, 0
+        self._last_audio_mixed = self._last_audio_exact = self._last_audio_hl = False
+        self._last_text_mfma = self._last_rank_cut = False
+        self._last_D_aud = self._last_q32 = self._last_qn2 = self._last_ints = self._last_gate_tables = None
+
+    def _knobs(self):
+        return Knobs(self.audio_precision, self.audio_kernel, self.text_kernel, self.tie_eps, self.mixed_single_launch,
+                     self.sharded_mixed, self.sharded_mixed_min_gflop, self.force_sharded, self.overlap_sweeps,
+                     self.text_after_sweep, self.audio_first, self.fused_pack, self.rank_cut, self.split_fuse,
+                     self.split_fuse_max_steps, self.host_ranks, self.use_wavvq)
+
+    def _facts(self):
+        db = self.db
+        return DBFacts(db.n_local, db.N, db.world, db.K, db.Ga, db.F, db.Dt, db.feature_dtype, db.hl_bound_ok,
+                       db.hl_image is not None, db.txt_sorted is not None, db.hl_planes)
+
     def _audio_grid(self):
         db = self.db
         if self.use_wavvq:
@@ -446,14 +575,13 @@ class CodeKNN:
         """Matching-step positions of a window: i = 0, 4*step, ... while i < n (GestureKNN.py:528,659);
         with the float wavvq step the literal accumulation is kept."""
         key = (self.n_db_frm, self.step_sz)
-        hit = self.__dict__.get("_qpos")
-        if hit is not None and hit[0] == key:          # (twice per clip, in front of its first launch)
-            return hit[1]
+        if self._qpos is not None and self._qpos[0] == key:          # (twice per clip, in front of its first launch)
+            return self._qpos[1]
         pos, i = [], 0
         while i < self.n_db_frm:
             pos.append(i)
             i += STEP_SZ * self.step_sz
-        self.__dict__["_qpos"] = (key, pos)
+        self._qpos = (key, pos)
         return pos
 
     # -- init (GestureKNN.py:462-473): same two draws from the (seeded) NumPy global stream ------
@@ -471,67 +599,80 @@ class CodeKNN:
         return code, np.concatenate((P[:, 0], P[:, 1]), axis=1).astype(np.float32)
 
     # -- batched sweeps ------------------------------------------------------------------------
-    def _hl_plan(self, sharded=False, Q=0):
-        """Will sweep_audio take the split-f16 (hl) mixed-precision path for a whole-clip sweep of Q queries on this DB
-        (the same conditions as sweep_audio's own; `sharded`: as a row shard inside sweep_tables)?"""
-        db = self.db
-        base = (self.audio_precision == "mixed" and self.tie_eps > 0 and db.n_local > 0 and db.K <= 512 and
-                db.hl_bound_ok and self.audio_kernel == "hl" and db.hl_image is not None)
-        if not sharded:
-            return base and db.world == 1
-        gflop = 2e-9 * Q * (-(-db.N // db.world) * db.Ga) * NUM_AUDIO_FEAT_FRAMES * db.F
-        return base and self.sharded_mixed and gflop >= self.sharded_mixed_min_gflop
+    def _tables_out(self, Q, dtype, out, with_rank):
+        """(dist, idx, rank, q_block, block_stride) a select writes: the views of the sharded path's exchange layout
+        `out` (written in place, merged after the collective) or new [Q,K] tables."""
+        K, dev = self.db.K, self.db.device
+        dist, idx, qb, bs = out if out is not None else (torch.empty((Q, K), dtype=dtype, device=dev),
+                                                         torch.empty((Q, K), dtype=torch.int32, device=dev), 0, 0)
+        return dist, idx, (torch.empty((Q, K), dtype=torch.int16, device=dev) if with_rank else None), qb, bs
+
+    def _select_plain(self, D, cand_code, C, G, out, with_rank):
+        """First-wins per-code minimum of a distance matrix D [Q, C] whose candidates lie on a grid of G positions per
+        window: (dist, idx, rank or None)."""
+        db, Q = self.db, D.shape[0]
+        dist, idx, rank, qb, bs = self._tables_out(Q, D.dtype, out, with_rank)
+        _lib.call("qpg_percode_select_f64" if D.dtype == torch.float64 else "qpg_percode_select_f32", db.device, D,
+                  D.stride(0), Q, cand_code, C, db.K, float(ABSENT_DIST), db.idx_base * G, dist, idx, rank, qb, bs)
+        return dist, idx, rank
+
+    def _finish(self, dist, idx, rank, want_rank, reduce):
+        """What the public sweeps return: the tables as they are (not reduce: a sharded caller combines several in one
+        exchange, sweep_tables), or min-reduced across ranks, with the ranks if asked."""
+        if not reduce:
+            return dist, idx
+        dist, idx = self._reduce_min(dist, idx)
+        if want_rank:
+            return dist, idx, (rank if rank is not None else self.rank_rows(dist))
+        return dist, idx
+
+    def _sweep_timer(self):
+        """The (start, end) events for this call's sweep kernel, or None (kernel_events off, or not this call's turn)."""
+        if self.kernel_events is None:
+            return None
+        if self.kernel_events_every > 1:
+            self._ev_calls += 1
+            if self._ev_calls % self.kernel_events_every:
+                return None
+        return (self.kernel_event_pool.pop() if self.kernel_event_pool else
+                (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
 
     def sweep_audio(self, qbase, q_win, q_t, tap_stride=None, want_rank=False, reduce=True, out=None, prepacked=None,
                     cut_top_n=None):
         """Per-code best audio candidate for every query: returns (dist f64 [Q,512], idx i32 [Q,512])
         with global candidate indices j*26+g (-1 = code absent), min-reduced across ranks; with
         want_rank also the stable ranks i16 [Q,512]."""
+        Q = int(q_win.shape[0]) if isinstance(q_win, torch.Tensor) else len(q_win)
+        plan = plan_audio(self._knobs(), self._facts(), Q, want_rank, reduce, out is not None, cut_top_n or 0)
+        r = self._sweep_audio(plan, qbase, q_win, q_t, tap_stride, out, prepacked)
+        return self._finish(r.dist, r.idx, r.rank, want_rank, reduce)
+
+    def _sweep_audio(self, plan, qbase, q_win, q_t, tap_stride=None, out=None, prepacked=None, sweep_event=None,
+                     after_sweep=None):
+        """The WavLM audio side as `plan` (an AudioPlan) says: query pack, sweep, select -> AudioResult.
+        prepacked = (q32, qn2, ...): sweep_tables packed the clip's whole query side in one launch.  Directly behind the
+        sweep kernel on the current stream: after_sweep() is called (ClipGraph: the encode leg forks there / the sweep
+        signal is raised) and sweep_event is recorded (sweep_tables: the text side starts behind the sweep)."""
         db, dev = self.db, self.db.device
         Q = int(q_win.shape[0]) if isinstance(q_win, torch.Tensor) else len(q_win)
         qbase = qbase.contiguous()
         M, T, F = qbase.shape
         ts = db.tap_stride if tap_stride is None else tap_stride
-        if prepacked is not None:           # (sweep_tables packed the clip's whole query side in one launch)
+        if prepacked is not None:
             q32, qn2 = prepacked[0], prepacked[1]
         else:
             q32 = torch.empty((Q, NUM_AUDIO_FEAT_FRAMES * F), dtype=torch.float32, device=dev)
             qn2 = torch.empty((Q,), dtype=torch.float64, device=dev)
         C = db.n_local * db.Ga
-        fused_rank = want_rank and db.world == 1
-        half = db.feature_dtype == "f16"
-        local_final = fused_rank and reduce and out is None               # one GPU: this select decides everything
-        shard_part = (db.world > 1 or self.force_sharded) and not reduce and out is not None   # row shard: sweep_tables merges
-        # (the same number on every rank — the largest shard's — so that all ranks take the same path: the mixed merge
-        # has two more collectives than the f64 one)
-        gflop = 2e-9 * Q * (-(-db.N // db.world) * db.Ga) * NUM_AUDIO_FEAT_FRAMES * db.F
-        mixed = (self.audio_precision == "mixed" and self.tie_eps > 0 and C > 0 and db.K <= 512 and db.hl_bound_ok and
-                 (local_final or (shard_part and self.sharded_mixed and gflop >= self.sharded_mixed_min_gflop)))
-        exact = self.audio_precision == "exact" and self.tie_eps > 0 and C > 0
-        self._last_audio_mixed, self._last_audio_exact = mixed, exact
-        self._last_rank_cut = False
+        mixed, use_hl, half = plan.path == "mixed", plan.kernel in ("hl", "hl1"), db.feature_dtype == "f16"
         # the mixed-precision sweep stores its matrix in f32: it only feeds the select's two streaming passes
         D = torch.empty((Q, max(C, 1)), dtype=torch.float32 if mixed else torch.float64, device=dev)
-        ev = getattr(self, "kernel_events", None)       # bench.py: HIP events around the dominant kernel
-        every = getattr(self, "kernel_events_every", 1)  # ... of every n-th call
-        if ev is not None and every > 1:
-            self._ev_calls = getattr(self, "_ev_calls", 0) + 1
-            if self._ev_calls % every:
-                ev = None
-        if ev is not None:
-            pool = getattr(self, "kernel_event_pool", None)      # events created ahead of the timed region
-            e0, e1 = pool.pop() if pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        use_hl = mixed and self.audio_kernel == "hl" and db.hl_image is not None
-        hl_fn = "qpg_audio_cosine_hl" if db.hl_planes == 2 else "qpg_audio_cosine_hl1"
-        self._last_audio_hl = use_hl
-        sweep_launch = None
+        timer = self._sweep_timer()
+        sweep_fn = "qpg_audio_cosine_" + plan.kernel
         if use_hl:                    # gather + norms + split-f16 image in ONE launch
-            nbq = int(_lib.load().qpg_audio_hl_query_bytes(Q, db.F))
-            qi = self.__dict__.get("_hl_qimage")
-            if qi is None or qi.numel() < nbq:
-                qi = self._hl_qimage = torch.empty((nbq,), dtype=torch.uint8, device=dev)
+            qi = self._hl_qimage = _grown(self._hl_qimage, int(_lib.load().qpg_audio_hl_query_bytes(Q, db.F)), dev)
             # the sweep's arguments are converted BEFORE the pack goes out: its launch follows the pack's at once
-            sweep_launch = _lib.prepare(hl_fn, dev, db.hl_image, db.n_local, db.F, db.Ga, db.cn2, qi,
+            sweep_launch = _lib.prepare(sweep_fn, dev, db.hl_image, db.n_local, db.F, db.Ga, db.cn2, qi,
                                         qn2, Q, D, 1, D.stride(0), self._guard_stats)
             if prepacked is None:
                 _lib.call("qpg_audio_pack_queries_hl", dev, qbase, M, T, F, _i32(q_win, dev), _i32(q_t, dev), Q,
@@ -540,51 +681,39 @@ class CodeKNN:
             assert prepacked is None, "the one-launch clip pack feeds the split-f16 sweep only"
             _lib.call("qpg_audio_pack_queries", dev, qbase, M, T, F, _i32(q_win, dev), _i32(q_t, dev), Q,
                       NUM_AUDIO_FEAT_FRAMES, ts, q32, qn2)
-        if ev is not None:
-            e0.record(torch.cuda.current_stream(dev))          # (the events bracket the sweep kernel alone)
-        if sweep_launch is not None:
+        if timer is not None:
+            timer[0].record(torch.cuda.current_stream(dev))          # (the events bracket the sweep kernel alone)
+        if use_hl:
             sweep_launch()
-        elif mixed:
-            _lib.call("qpg_audio_cosine_mx_h" if half else "qpg_audio_cosine_mx", dev, db.base, db.n_local, db.T, db.F, db.aud_t, db.Ga,
-                      NUM_AUDIO_FEAT_FRAMES, db.tap_stride, db.cn2, q32, qn2, Q, D, 1, D.stride(0), self._guard_stats)
         else:
-            _lib.call("qpg_audio_cosine_f64" if db.feature_dtype == "f32" else "qpg_audio_cosine_f64_h", dev, db.base,
-                      db.n_local, db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, db.cn2, q32, qn2,
-                      Q, D, D.stride(0))
-        if ev is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            ev.append((e0, e1))
-        hook = self.__dict__.get("after_sweep")          # (ClipGraph: the encode leg forks here, behind the sweep kernel)
-        if hook is not None:
-            hook()
-        if getattr(self, "_want_sweep_event", False):    # sweep_tables: the text side starts behind the sweep
-            self._record_sweep_event(dev)
-        if out is not None:          # exchange layout of the sharded path: written in place, merged after the collective
-            dist, idx, qb, bs = out
+            strides = (1, D.stride(0), self._guard_stats) if mixed else (D.stride(0),)     # (mx: + the trouble word)
+            _lib.call(sweep_fn, dev, db.base, db.n_local, db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES,
+                      db.tap_stride, db.cn2, q32, qn2, Q, D, *strides)
+        if timer is not None:
+            timer[1].record(torch.cuda.current_stream(dev))
+            self.kernel_events.append(timer)
+        if after_sweep is not None:
+            after_sweep()
+        if sweep_event is not None:
+            sweep_event.record(torch.cuda.current_stream(dev))
+        if plan.path == "plain":
+            dist, idx, rank = self._select_plain(D, db.aud_cand_code, C, db.Ga, out, plan.fused_rank)
         else:
-            dist = torch.empty((Q, db.K), dtype=torch.float64, device=dev)
-            idx = torch.empty((Q, db.K), dtype=torch.int32, device=dev)
-            qb = bs = 0
-        rank = torch.empty((Q, db.K), dtype=torch.int16, device=dev) if fused_rank else None
+            dist, idx, rank, qb, bs = self._tables_out(Q, torch.float64, out, plan.fused_rank)
+            tables = (Q, db.aud_cand_code, C, db.K, float(ABSENT_DIST), db.idx_base * db.Ga, dist, idx, rank, qb, bs)
+            # what the guards re-evaluate a pair from, in the reference's own arithmetic
+            track = (db.base, db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, q32)
         if mixed:
-            need = int(_lib.load().qpg_percode_select_mixed_ws_bytes(Q, db.K))
-            ws = getattr(self, "_mix_ws", None)
-            if ws is None or ws.numel() < need:
-                # (zero-filled ONCE: the select's streamed state is all-zero between launches, qpg.h)
-                ws = self._mix_ws = torch.zeros((need,), dtype=torch.uint8, device=dev)
-            self._last_mix_Q = Q
-            sel_args = (D, 1, D.stride(0), Q, db.aud_cand_code, C, db.K,
-                        float(ABSENT_DIST), db.idx_base * db.Ga, dist, idx, rank, qb, bs, db.base, db.T, db.F, db.aud_t,
-                        db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, q32, qn2, db.cn2,
-                        AUDIO_HL_BAND if use_hl else AUDIO_MX_BAND, float(self.tie_eps),
-                        self._guard_stats, None if self.mixed_single_launch else ws,
-                        0 if self.mixed_single_launch else ws.numel(), int(half))
-            use_cut = cut_top_n in (1, 2) and local_final and rank is not None and not self.mixed_single_launch
-            self._last_rank_cut = use_cut
+            # (zero-filled ONCE: the select's streamed state is all-zero between launches, qpg.h)
+            ws = self._mix_ws = _grown(self._mix_ws, int(_lib.load().qpg_percode_select_mixed_ws_bytes(Q, db.K)), dev,
+                                       zero=True)
+            single = self.mixed_single_launch        # the select's tier-1 work inside one launch: no workspace
+            sel_args = (D, 1, D.stride(0), *tables, *track, qn2, db.cn2, plan.band, float(self.tie_eps),
+                        self._guard_stats, None if single else ws, 0 if single else ws.numel(), int(half))
             try:
-                if use_cut:
+                if plan.cut_top_n:
                     _lib.call("qpg_percode_select_mixed_f64_cut", dev, *sel_args, db.pos_rank_t, db.freq_rank,
-                              int(cut_top_n), int(self.rank_cut_probe))
+                              int(plan.cut_top_n), int(self.rank_cut_probe))
                 else:
                     _lib.call("qpg_percode_select_mixed_f64", dev, *sel_args)
             except Exception:
@@ -592,40 +721,23 @@ class CodeKNN:
                 # later clips consume silently (the kernels only restore the all-zero state when all of them ran)
                 self._mix_ws = None
                 raise
-        elif exact:
-            need = int(_lib.load().qpg_percode_select_exact_ws_bytes(Q, C, db.K))
-            ws = getattr(self, "_exact_ws", None)
-            if ws is None or ws.numel() < need:
-                ws = self._exact_ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-            _lib.call("qpg_percode_select_exact_f64", dev, D, D.stride(0), Q, db.aud_cand_code, C, db.K,
-                      float(ABSENT_DIST), db.idx_base * db.Ga, dist, idx, rank, qb, bs, db.base, db.T, db.F, db.aud_t,
-                      db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, q32, float(self.tie_eps), self._guard_stats, int(half),
-                      ws, ws.numel())
-        elif self.tie_eps > 0 and C > 0:
-            _lib.call("qpg_percode_select_guarded_f64", dev, D, D.stride(0), Q, db.aud_cand_code, C, db.K,
-                      float(ABSENT_DIST), db.idx_base * db.Ga, dist, idx, rank, qb, bs, db.base, db.T, db.F, db.aud_t,
-                      db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, q32, float(self.tie_eps), self._guard_stats, int(half))
-        else:
-            _lib.call("qpg_percode_select_f64", dev, D, D.stride(0), Q, db.aud_cand_code, C, db.K, float(ABSENT_DIST),
-                      db.idx_base * db.Ga, dist, idx, rank, qb, bs)
-        self._last_D_aud = D
-        self._last_q32, self._last_qn2 = q32, qn2          # the sharded mixed merge re-evaluates requested pairs from these
-        if not reduce:              # sharded caller combines several tables in one exchange (sweep_tables)
-            return dist, idx
-        dist, idx = self._reduce_min(dist, idx)
-        if want_rank:
-            return dist, idx, (rank if fused_rank else self.rank_rows(dist))
-        return dist, idx
+        elif plan.path == "exact":
+            ws = self._exact_ws = _grown(self._exact_ws, int(_lib.load().qpg_percode_select_exact_ws_bytes(Q, C, db.K)),
+                                         dev)
+            _lib.call("qpg_percode_select_exact_f64", dev, D, D.stride(0), *tables, *track, float(self.tie_eps),
+                      self._guard_stats, int(half), ws, ws.numel())
+        elif plan.path == "guarded":
+            _lib.call("qpg_percode_select_guarded_f64", dev, D, D.stride(0), *tables, *track, float(self.tie_eps),
+                      self._guard_stats, int(half))
+        self._last_audio_mixed, self._last_audio_exact, self._last_audio_hl = mixed, plan.path == "exact", use_hl
+        self._last_rank_cut, self._last_D_aud, self._last_q32, self._last_qn2 = plan.cut_top_n > 0, D, q32, qn2
+        if mixed:
+            self._last_mix_Q = Q
+        return AudioResult(dist, idx, rank, D, q32, qn2, plan)
 
-    def _record_sweep_event(self, dev):
-        if self.__dict__.get("_sweep_event") is None:
-            self._sweep_event = torch.cuda.Event()                      # one event, re-recorded by every clip
-        self._sweep_done = self._sweep_event
-        self._sweep_done.record(torch.cuda.current_stream(dev))
-
-    def sweep_text(self, queries, want_rank=False, reduce=True, normalised=False, out=None, cols_packed=False):
+    def sweep_text(self, queries, want_rank=False, reduce=True, normalised=False, out=None, cols_packed=False, kind=None):
         """queries: f32 [Q,384] on the device (already sklearn-normalised if `normalised`).
-        Returns (dist f32 [Q,512], idx i32 [Q,512][, rank])."""
+        Returns (dist f32 [Q,512], idx i32 [Q,512][, rank]).  kind: what plan_text planned for this call (sweep_tables)."""
         db, dev = self.db, self.db.device
         Q = queries.shape[0]
         if normalised:
@@ -633,40 +745,20 @@ class CodeKNN:
         else:
             qn = torch.empty_like(queries)
             _lib.call("qpg_l2_normalize_rows_f32", dev, queries, Q, db.Dt, qn)
-        self._last_text_mfma = False
-        if (self.text_kernel == "mfma" and db.txt_sorted is not None and Q > 0 and self.audio_precision != "exact" and
-                ((out is None and reduce and db.world == 1) or (out is not None and not reduce))):
-            self._last_text_mfma = True
-            if out is not None:           # row shard: straight into the exchange buffer, global indices, merged later
-                dist, idx, qb, bs = out
-                db.txt_sorted.select(qn, float(ABSENT_DIST), self._guard_stats, dist=dist, idx=idx,
-                                     idx_base=db.idx_base * db.Gt, q_block=qb, block_stride=bs, scratch=self._txt_scratch,
-                                     cols_packed=cols_packed)
-                return dist, idx
-            rank = torch.empty((Q, db.K), dtype=torch.int16, device=dev) if want_rank else None
-            dist, idx, _ = db.txt_sorted.select(qn, float(ABSENT_DIST), self._guard_stats, rank=rank,
-                                                scratch=self._txt_scratch, cols_packed=cols_packed)
-            if want_rank:
-                return dist, idx, rank
-            return dist, idx
-        D = torch.empty((Q, max(db.Ct, 1)), dtype=torch.float32, device=dev)
-        _lib.call("qpg_text_cosine_f32", dev, db.ctxt, db.Ct, db.Dt, qn, Q, D, D.stride(0))
-        if out is not None:
-            dist, idx, qb, bs = out
+        if kind is None:
+            kind = plan_text(self._knobs(), self._facts(), Q, reduce, out is not None)
+        self._last_text_mfma = kind == "mfma"
+        if kind == "mfma":
+            # (row shard: straight into the exchange buffer, global indices, merged later; one GPU: idx_base is 0)
+            dist, idx, rank, qb, bs = self._tables_out(Q, torch.float32, out, want_rank and out is None)
+            db.txt_sorted.select(qn, float(ABSENT_DIST), self._guard_stats, dist=dist, idx=idx, rank=rank,
+                                 idx_base=db.idx_base * db.Gt, q_block=qb, block_stride=bs, scratch=self._txt_scratch,
+                                 cols_packed=cols_packed)
         else:
-            dist = torch.empty((Q, db.K), dtype=torch.float32, device=dev)
-            idx = torch.empty((Q, db.K), dtype=torch.int32, device=dev)
-            qb = bs = 0
-        fused_rank = want_rank and db.world == 1
-        rank = torch.empty((Q, db.K), dtype=torch.int16, device=dev) if fused_rank else None
-        _lib.call("qpg_percode_select_f32", dev, D, D.stride(0), Q, db.txt_cand_code, db.Ct, db.K, float(ABSENT_DIST),
-                  db.idx_base * db.Gt, dist, idx, rank, qb, bs)
-        if not reduce:              # sharded caller combines several tables in one exchange (sweep_tables)
-            return dist, idx
-        dist, idx = self._reduce_min(dist, idx)
-        if want_rank:
-            return dist, idx, (rank if fused_rank else self.rank_rows(dist))
-        return dist, idx
+            D = torch.empty((Q, max(db.Ct, 1)), dtype=torch.float32, device=dev)
+            _lib.call("qpg_text_cosine_f32", dev, db.ctxt, db.Ct, db.Dt, qn, Q, D, D.stride(0))
+            dist, idx, rank = self._select_plain(D, db.txt_cand_code, db.Ct, db.Gt, out, want_rank and db.world == 1)
+        return self._finish(dist, idx, rank, want_rank, reduce)
 
     def sweep_audio_wavvq(self, test_wavvq, q_win, q_t, want_rank=False, reduce=True, out=None):
         """vq-wav2vec audio sweep: test_wavvq (M,398,2) ints (device tensor or array).  Distances are exact
@@ -680,23 +772,9 @@ class CodeKNN:
         taps = (ctypes.c_int32 * len(db.vq_taps))(*db.vq_taps)
         _lib.call("qpg_wavvq_lev_f32", dev, db.vq_sym, db.n_local, db.Tv, db.vq_t, db.Gv, taps, len(db.vq_taps),
                   sym_q, sym_q.shape[0], sym_q.shape[1], _i32(q_win, dev), _i32(q_t, dev), Q, D, D.stride(0))
-        if out is not None:
-            dist, idx, qb, bs = out
-        else:
-            dist = torch.empty((Q, db.K), dtype=torch.float32, device=dev)
-            idx = torch.empty((Q, db.K), dtype=torch.int32, device=dev)
-            qb = bs = 0
-        fused_rank = want_rank and db.world == 1
-        rank = torch.empty((Q, db.K), dtype=torch.int16, device=dev) if fused_rank else None
-        _lib.call("qpg_percode_select_f32", dev, D, D.stride(0), Q, db.vq_cand_code, C, db.K, float(ABSENT_DIST),
-                  db.idx_base * db.Gv, dist, idx, rank, qb, bs)
+        dist, idx, rank = self._select_plain(D, db.vq_cand_code, C, db.Gv, out, want_rank and db.world == 1)
         self._last_D_aud = D
-        if not reduce:              # sharded caller combines several tables in one exchange (sweep_tables)
-            return dist, idx
-        dist, idx = self._reduce_min(dist, idx)
-        if want_rank:
-            return dist, idx, (rank if fused_rank else self.rank_rows(dist))
-        return dist, idx
+        return self._finish(dist, idx, rank, want_rank, reduce)
 
     def _reduce_min(self, dist, idx):
         """Cross-shard min + index: all-reduce(MIN) on the distances, then
@@ -721,8 +799,7 @@ class CodeKNN:
     def tier1_list_lengths(self):
         """Entries of every query's tier-1 re-evaluation list in the last mixed-precision select (capacity 2048 each):
         read back from the select's workspace.  Diagnostics (bench.py --data speechlike, tests): what the caps see."""
-        ws = getattr(self, "_mix_ws", None)
-        Q = getattr(self, "_last_mix_Q", 0)
+        ws, Q = self._mix_ws, self._last_mix_Q
         if ws is None or not Q:
             return np.zeros((0,), np.int64)
         K = self.db.K
@@ -810,7 +887,51 @@ class CodeKNN:
     def n_steps(self):
         return len(self.query_positions())
 
-    def sweep_tables(self, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, owner_blocks=False, for_walk=False):
+    def _query_index(self, M):
+        """(window, frame, context row) of every query of M windows: device tensors, built once per clip length (also
+        keeps H2D copies out of graphs)."""
+        if M not in self._qcache:
+            pos, dev = self.query_positions(), self.db.device
+            qw = np.repeat(np.arange(M), len(pos))
+            qt = np.tile(np.array([int(i) for i in pos]), M)                  # clip_test[int(i)]  (:559, :565)
+            rows_ = [int(i / self.n_db_frm * 30) for i in pos] * M           # GestureKNN.py:549, 551
+            self._qcache[M] = (_i32(qw, dev), _i32(qt, dev), _i32(np.asarray(rows_), dev))
+        return self._qcache[M]
+
+    def _fork_side(self):
+        """The side stream, started behind everything enqueued on the current stream so far."""
+        dev = self.db.device
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(dev)
+            # (wait_stream() makes a new event per call; two cached events do the same for ~5 us less host time per
+            # clip, most of it in front of the step's first launch)
+            self._side_gate, self._side_done = torch.cuda.Event(), torch.cuda.Event()
+            self._sweep_event = torch.cuda.Event()          # (the end of the audio sweep: re-recorded by every clip)
+        if dev.index is None or dev.index == torch.cuda.current_device():
+            self._side_gate.record()            # (the current stream: no Stream object in front of the step's launches)
+        else:
+            self._side_gate.record(torch.cuda.current_stream(dev))
+        self._side_stream.wait_event(self._side_gate)
+        return self._side_stream
+
+    def _clip_pack(self, test_interp, test_context, q_win, q_t, q_row, Q):
+        """The clip's WHOLE query side in one launch (qpg_clip_pack_hl: the audio gather / norms / split-f16 image AND
+        the text queries' gather / sklearn normalisation / column image) -> (q32, qn2, qn).  Behind the 32-row sweep,
+        which holds every register of every CU, two separate text packs would not get a wave slot before it is over."""
+        db, dev = self.db, self.db.device
+        q32 = torch.empty((Q, NUM_AUDIO_FEAT_FRAMES * db.F), dtype=torch.float32, device=dev)
+        qn2 = torch.empty((Q,), dtype=torch.float64, device=dev)
+        qi = self._hl_qimage = _grown(self._hl_qimage, int(_lib.load().qpg_audio_hl_query_bytes(Q, db.F)), dev)
+        qn = torch.empty((Q, db.Dt), dtype=torch.float32, device=dev)
+        cols = db.txt_sorted.cols_buffer(Q, self._txt_scratch)
+        tc, ti = test_context.contiguous(), test_interp.contiguous()
+        _lib.call("qpg_clip_pack_hl", dev, ti, ti.shape[0], db.T, db.F, q_win, q_t, Q, NUM_AUDIO_FEAT_FRAMES,
+                  db.tap_stride, q32, qn2, qi, qi.numel(), tc, tc.shape[0], tc.shape[1], db.Dt, q_win, q_row, Q, qn, cols,
+                  cols.numel())
+        return q32, qn2, qn
+
+    def sweep_tables(self, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, owner_blocks=False, for_walk=False,
+                     after_sweep=None):
         """Both batched sweeps + ranks for all Q = n_windows*steps query positions (the windows may
         belong to several clips).  test_interp: f32 [M,180,F]; test_context: f32 [M,30,384] (device).
         Returns a dict of device tensors: aud_d/aud_idx/aud_rank, txt_d/txt_idx/txt_rank.
@@ -818,101 +939,52 @@ class CodeKNN:
         tables of block `rank` — one all-to-all instead of two all-reduces; the returned tables then hold only that
         block's Q/world rows.
         for_walk: the tables go straight into walk() and nowhere else - the audio select may then leave unsettled what the
-        walk can not read (CodeKNN.rank_cut; the returned tables are exact only where the walk reads them)."""
+        walk can not read (CodeKNN.rank_cut; the returned tables are exact only where the walk reads them).
+        after_sweep: called directly behind the WavLM audio sweep kernel's launch (ClipGraph forks its encode leg /
+        raises its sweep signal there); the wavvq sweep does not call it."""
         db, dev = self.db, self.db.device
         M, steps = n_windows, self.n_steps()
         if test_interp.shape[0] < M or (mode != MODE_AUD and test_context.shape[0] < M):
             # the reference indexes test_wavlm_feat[i] / test_context[i] for i < n_test_seq (GestureKNN.py:788-800)
             raise IndexError("n_windows=%d but the test arrays hold %d audio / %d context windows"
                              % (M, test_interp.shape[0], test_context.shape[0]))
-        if self.use_wavvq:
-            ok = tuple(test_interp.shape[1:]) == (db.Tv, 2)
-        else:
-            ok = tuple(test_interp.shape[1:]) == (db.T, db.F)
-        if not ok:
+        want = (db.Tv, 2) if self.use_wavvq else (db.T, db.F)
+        if tuple(test_interp.shape[1:]) != want:
             raise ValueError("test audio windows have shape %s, database expects %s"
-                             % (tuple(test_interp.shape[1:]), (db.Tv, 2) if self.use_wavvq else (db.T, db.F)))
-        pos = self.query_positions()
-        cache = self.__dict__.setdefault("_qcache", {})
-        if M not in cache:          # index tensors are built once per clip length (also keeps H2D copies out of graphs)
-            qw = np.repeat(np.arange(M), steps)
-            qt = np.tile(np.array([int(i) for i in pos]), M)                  # clip_test[int(i)]  (:559, :565)
-            rows_ = [int(i / self.n_db_frm * 30) for i in pos] * M           # GestureKNN.py:549, 551
-            cache[M] = (_i32(qw, dev), _i32(qt, dev), _i32(np.asarray(rows_), dev))
-        q_win, q_t, q_row = cache[M]
+                             % (tuple(test_interp.shape[1:]), want))
+        q_win, q_t, q_row = self._query_index(M)
+        Q = M * steps
+        key = (self._knobs(), self._facts(), M, steps, mode, for_walk, owner_blocks)     # (every value the plan reads)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = plan_step(*key)
+        sharded = plan.sharded
         T = dict(aud_d=None, aud_idx=None, aud_rank=None, txt_d=None, txt_idx=None, txt_rank=None)
-        sharded = db.world > 1 or self.force_sharded
-        # Round 5: the rank fusion in front of the walk is two independent argmins (audio order, text order:
-        # GestureKNN.py:574-576, :553-555) - each side's half is launched behind its own select on its own stream
-        # (qpg_fuse_best_ranked) into the walk's gate tables, which the walk then takes as they are (QPG_MODE_PREFUSED):
-        # the join of the two streams has half a rank fusion less behind it.  split_fuse = False: one launch in the walk.
-        # (a clip or a few: the fusion is one latency-bound round of blocks and the critical path loses 3-4 us; 16 clips'
-        # worth of steps are throughput-bound and two launches buy nothing: experiments/round_scripts/r05_ab_split.sh)
-        split = (for_walk and mode == MODE_AUD_TXT and not sharded and not self.host_ranks and self.split_fuse and
-                 db.K % 16 == 0 and db.K <= 4096 and M * steps <= self.split_fuse_max_steps)
-        gtab = torch.empty((3, max(M, 1) * steps, db.K), dtype=torch.int32, device=dev) if split else None
-        lay = None
-        if sharded:
-            # per-shard tables go straight into the exchange buffer (ExchangeLayout); merged after ONE collective
-            parts = [p_ for p_, on in (("aud", mode in (MODE_AUD_TXT, MODE_AUD)), ("txt", mode in (MODE_AUD_TXT, MODE_TXT)))
-                     if on]
-            lkey = (M * steps, db.world if owner_blocks else 1, tuple(parts), not self.use_wavvq)
-            lays = self.__dict__.setdefault("_layouts", {})
-            lay = lays.get(lkey)
-            if lay is None:             # one send buffer per shape, reused by every clip (stream-ordered: the previous
-                lay = lays[lkey] = ExchangeLayout(lkey[0], db.K, lkey[1], parts, lkey[3], dev)   # clip's exchange read it)
-        # The two sweeps are independent until the walk and lean on different pipes (f64 matrix cores vs f32
-        # VALU): with both modalities on, the text side runs on a second HIP stream underneath the audio sweep.
-        overlap = mode == MODE_AUD_TXT and self.overlap_sweeps
-        if overlap:
-            side = self.__dict__.get("_side_stream")
-            if side is None:
-                side = self.__dict__["_side_stream"] = torch.cuda.Stream(dev)
-            # (wait_stream() makes a new event per call; two cached events do the same for ~5 us less host time per clip,
-            # most of it in front of the step's first launch)
-            gate = self.__dict__.get("_side_gate")
-            if gate is None:
-                gate = self.__dict__["_side_gate"] = torch.cuda.Event()
-                self.__dict__["_side_done"] = torch.cuda.Event()
-            if dev.index is None or dev.index == torch.cuda.current_device():
-                gate.record()                   # (the current stream: no Stream object in front of the step's launches)
-            else:
-                gate.record(torch.cuda.current_stream(dev))
-            side.wait_event(gate)
-
-        # Round 4: the clip's WHOLE query side in one launch (qpg_clip_pack_hl: the audio gather / norms / split-f16 image
-        # AND the text queries' gather / sklearn normalisation / column image) when both sides take their matrix-core
-        # paths (one GPU or a row shard).  Behind the 32-row sweep, which holds every register of every CU, the text side's two
-        # tiny pack launches did not get a wave slot before the sweep was over.
-        mfma_text_ = (self.text_kernel == "mfma" and db.txt_sorted is not None and self.audio_precision != "exact")
+        # split fusion: the rank fusion in front of the walk is two independent argmins (audio order, text order:
+        # GestureKNN.py:574-576, :553-555) - each side's half goes out behind its own select on its own stream
+        # (qpg_fuse_best_ranked) into the walk's gate tables, which the walk then takes as they are (QPG_MODE_PREFUSED)
+        gtab = torch.empty((3, max(M, 1) * steps, db.K), dtype=torch.int32, device=dev) if plan.split_fuse else None
+        # sharded: the per-shard tables go straight into the exchange buffer (ExchangeLayout)
+        lay = self._layout(Q, owner_blocks, mode) if sharded else None
+        # The two sweeps are independent until the walk: with both modalities on, the text side runs on a second HIP
+        # stream beside the audio side
+        side = self._fork_side() if plan.overlap else None
         packed = None
-        if (overlap and not self.use_wavvq and mfma_text_ and self._hl_plan(sharded, M * steps) and db.Dt % 128 == 0 and
-                self.fused_pack):
-            Qn = M * steps
-            q32_ = torch.empty((Qn, NUM_AUDIO_FEAT_FRAMES * db.F), dtype=torch.float32, device=dev)
-            qn2_ = torch.empty((Qn,), dtype=torch.float64, device=dev)
-            nbq = int(_lib.load().qpg_audio_hl_query_bytes(Qn, db.F))
-            qi_ = self.__dict__.get("_hl_qimage")
-            if qi_ is None or qi_.numel() < nbq:
-                qi_ = self._hl_qimage = torch.empty((nbq,), dtype=torch.uint8, device=dev)
-            qn_ = torch.empty((Qn, db.Dt), dtype=torch.float32, device=dev)
-            cols_ = db.txt_sorted.cols_buffer(Qn, self._txt_scratch)
-            tc_ = test_context.contiguous()
-            ti_ = test_interp.contiguous()
-            _lib.call("qpg_clip_pack_hl", dev, ti_, ti_.shape[0], db.T, db.F, q_win, q_t, Qn,
-                      NUM_AUDIO_FEAT_FRAMES, db.tap_stride, q32_, qn2_, qi_, qi_.numel(), tc_, tc_.shape[0], tc_.shape[1],
-                      db.Dt, q_win, q_row, Qn, qn_, cols_, cols_.numel())
-            packed = (q32_, qn2_, qn_)
-            # the side stream starts BEHIND the pack
-            gate = self.__dict__["_side_gate"]
-            gate.record(torch.cuda.current_stream(dev))
-            side.wait_event(gate)
+        if plan.clip_pack:
+            packed = self._clip_pack(test_interp, test_context, q_win, q_t, q_row, Q)
+            self._side_gate.record(torch.cuda.current_stream(dev))          # the side stream starts BEHIND the pack
+            side.wait_event(self._side_gate)
+
+        def keep(p_, g, r):          # a side's tables + its half of the rank fusion, on the stream its select ran on
+            T[p_ + "_d"], T[p_ + "_idx"], T[p_ + "_rank"] = r[0], r[1], (None if sharded else r[2])
+            if gtab is not None:
+                _lib.call("qpg_fuse_best_ranked", dev, r[2], r[1], db.pos_rank, db.freq_rank, Q, db.K, gtab[g])
 
         def text_pack():
             # gather clip_context[int(i/n*30)] of every step + sklearn normalisation in one launch
             tc = test_context.contiguous()
-            qn = torch.empty((M * steps, db.Dt), dtype=torch.float32, device=dev)
-            _lib.call("qpg_text_pack_queries_f32", dev, tc, tc.shape[0], tc.shape[1], db.Dt, q_win, q_row, M * steps, qn)
+            qn = torch.empty((Q, db.Dt), dtype=torch.float32, device=dev)
+            _lib.call("qpg_text_pack_queries_f32", dev, tc, tc.shape[0], tc.shape[1], db.Dt, q_win, q_row, Q, qn)
             return qn
 
         def text_side(qn=None):
@@ -920,114 +992,46 @@ class CodeKNN:
                 qn = packed[2]
             elif qn is None:
                 qn = text_pack()
-            r = self.sweep_text(qn, want_rank=not sharded, reduce=not sharded, normalised=True,
-                                out=lay.views("txt") if sharded else None, cols_packed=packed is not None)
-            T["txt_d"], T["txt_idx"] = r[0], r[1]
-            if not sharded:
-                T["txt_rank"] = r[2]
-            if gtab is not None:            # (on the stream the text select ran on)
-                _lib.call("qpg_fuse_best_ranked", dev, T["txt_rank"], T["txt_idx"], db.pos_rank, db.freq_rank, M * steps,
-                          db.K, gtab[1])
-        # Order of the two sides (both modalities on).  Round 1 enqueued the text side first: its kernels ran while the
-        # host was still enqueueing the audio side, but its sweep (all CUs, ~56 us) then delayed the audio sweep by as
-        # much; with the audio side first and no ordering between the streams the two sweeps contend for the same CUs
-        # (`audio_first`, kept for measurements: no faster).  Now (`text_after_sweep`): audio side first, and the text
-        # sweep waits on its own stream for the END of the audio sweep, so that it fills the CUs the audio select leaves
-        # idle (one block per query, ~90 us): 0.58 -> 0.555 ms per clip.
-        # text_after_sweep: the audio side is enqueued first and the text side waits (on its own stream) for the END of
-        # the audio sweep: the text sweep then fills the CUs the audio select leaves idle (one block per query) instead
-        # of delaying the audio sweep by its own duration at the start of the clip.
-        # Round 3: the text side on the matrix-core prefilter is ~60 us of small launches and the audio select now runs on
-        # every CU, so behind the sweep the text side became the longer of the two chains.  audio_first (None = auto: on
-        # with the matrix-core text side): the text side is enqueued behind the audio side's launches on its own stream
-        # with NO ordering - its GEMM trickles through under the sweep and the tables are ready before the audio select
-        # is.  bench.py, alternating in one run (tools/try_orders.sh), ms per clip: behind the sweep 0.400-0.404,
-        # text first 0.384-0.408, audio_first 0.360-0.374.
-        # (Enqueueing the text side even earlier - between the sweep's launch and the select's - starts its GEMM 50 us
-        # sooner and costs the sweep 25 us: 197 instead of 172.)
-        mfma_text = self.text_kernel == "mfma" and db.txt_sorted is not None and self.audio_precision != "exact"
-        audio_first = getattr(self, "audio_first", None)
-        audio_first = mfma_text if audio_first is None else bool(audio_first)
-        after = overlap and self.text_after_sweep and not audio_first and not self.use_wavvq
-        qn_early = None
-        if overlap and not audio_first and not after:
+            keep("txt", 1, self.sweep_text(qn, want_rank=not sharded, reduce=not sharded, normalised=True,
+                                           out=lay.views("txt") if sharded else None, cols_packed=packed is not None,
+                                           kind=plan.text))
+
+        # The planned order of the two sides (DESIGN.md section 4.2 has the measurements): "text_first": the text side is
+        # enqueued first; "text_after_sweep": audio side first, the text side waits on its stream for the END of the
+        # audio sweep and fills the CUs the audio select leaves idle; "audio_first": audio side first, no ordering
+        # between the streams - the text GEMM trickles through under the sweep.
+        if plan.order == "text_first":
             with torch.cuda.stream(side):
                 text_side()
-        if mode in (MODE_AUD_TXT, MODE_AUD):
-            fn = self.sweep_audio_wavvq if self.use_wavvq else self.sweep_audio
-            self._want_sweep_event, self._sweep_done = after, None
-            kw = {"prepacked": packed} if (packed is not None and not self.use_wavvq) else {}
-            if (for_walk and self.rank_cut and not sharded and not self.use_wavvq and not self.host_ranks and
-                    mode in (MODE_AUD_TXT, MODE_AUD)):
-                kw["cut_top_n"] = 1 if mode == MODE_AUD_TXT else 2
-            r = fn(test_interp, q_win, q_t, want_rank=not sharded, reduce=not sharded,
-                   out=lay.views("aud") if sharded else None, **kw)
-            self._want_sweep_event = False
-            T["aud_d"], T["aud_idx"] = r[0], r[1]
-            if not sharded:
-                T["aud_rank"] = r[2]
-            if gtab is not None:
-                _lib.call("qpg_fuse_best_ranked", dev, T["aud_rank"], T["aud_idx"], db.pos_rank, db.freq_rank, M * steps,
-                          db.K, gtab[0])
-        if after:
+        aud = None
+        if mode != MODE_TXT:
+            out = lay.views("aud") if sharded else None
+            if self.use_wavvq:
+                r = self.sweep_audio_wavvq(test_interp, q_win, q_t, want_rank=not sharded, reduce=not sharded, out=out)
+            else:
+                aud = self._sweep_audio(plan.audio, test_interp, q_win, q_t, out=out, prepacked=packed,
+                                        sweep_event=self._sweep_event if plan.order == "text_after_sweep" else None,
+                                        after_sweep=after_sweep)
+                r = self._finish(aud.dist, aud.idx, aud.rank, not sharded, not sharded)
+            keep("aud", 0, r)
+        if plan.order == "text_after_sweep":
             with torch.cuda.stream(side):
                 qn_early = None if packed is not None else text_pack()    # one small block, next to the audio sweep
-            if self._sweep_done is not None:
-                side.wait_event(self._sweep_done)
-            with torch.cuda.stream(side):
+                side.wait_event(self._sweep_event)
                 text_side(qn_early)
-        elif overlap and audio_first:
+        elif plan.order == "audio_first":
             with torch.cuda.stream(side):
                 text_side()
-        if overlap:
-            done = self.__dict__["_side_done"]
-            done.record(side)
-            torch.cuda.current_stream(dev).wait_event(done)
+        if plan.overlap:
+            self._side_done.record(side)
+            torch.cuda.current_stream(dev).wait_event(self._side_done)
             # The text tables are allocated on `side` and consumed on `main`.  No record_stream() (measured +15 us per
             # clip for the allocator's events): a freed block can only be reused by a later `side` allocation, and every
             # use of `side` starts by waiting for `main` above, i.e. after main's consumers of the block.
-        elif mode in (MODE_AUD_TXT, MODE_TXT):
+        elif mode != MODE_AUD:
             text_side()
         if sharded:
-            # ONE collective for both modalities (all-to-all when every rank only needs its own clip's rows, all-gather
-            # otherwise), then one merge launch per modality: min distance, lowest global index among equals, ranks.
-            # The trouble word rides in the blocks (ExchangeLayout "flags"): stamped here, ORed in by the receivers.
-            _lib.call("qpg_flags_stamp", dev, lay.send, lay.nblk, lay.block_bytes, lay.off["flags"], self._guard_stats)
-            recv = exchange_bytes(lay.send, db.world, owner_blocks)
-            src_stride = lay.block_bytes if owner_blocks else lay.send.numel()
-            gathered = False
-            for p_ in lay.parts:
-                f64 = lay.dtype[p_] == torch.float64
-                d = torch.empty((lay.Qb, db.K), dtype=lay.dtype[p_], device=dev)
-                ix = torch.empty((lay.Qb, db.K), dtype=torch.int32, device=dev)
-                rk = torch.empty((lay.Qb, db.K), dtype=torch.int16, device=dev)
-                wavlm_aud = p_ == "aud" and not self.use_wavvq
-                if wavlm_aud and getattr(self, "_last_audio_mixed", False):
-                    self._merge_mixed(recv, src_stride, lay, owner_blocks, d, ix, rk)
-                    gathered = True
-                elif wavlm_aud and getattr(self, "_last_audio_exact", False):
-                    self._merge_mixed(recv, src_stride, lay, owner_blocks, d, ix, rk, exact=True)
-                    gathered = True
-                elif f64:
-                    # (f64 sweep + capped guard per shard: near-ties ACROSS shards / codes are detected here and
-                    # re-matched on the exact path; exact integer distances of the wavvq mode need no guard)
-                    guard = wavlm_aud and self.tie_eps > 0
-                    _lib.call("qpg_merge_select_f64", dev, recv, db.world, src_stride, lay.off[p_ + "_d"],
-                              lay.off[p_ + "_i"], lay.Qb, db.K, float(ABSENT_DIST), d, ix, rk,
-                              float(self.tie_eps) if guard else 0.0, self._guard_stats if guard else None)
-                else:
-                    _lib.call("qpg_merge_select_f32", dev, recv, db.world, src_stride,
-                              lay.off[p_ + "_d"], lay.off[p_ + "_i"], lay.Qb, db.K, float(ABSENT_DIST), d, ix, rk)
-                T[p_ + "_d"], T[p_ + "_idx"], T[p_ + "_rank"] = d, ix, rk
-            if not gathered:            # (the mixed merge's prologue ORs the received words in itself)
-                _lib.call("qpg_flags_gather", dev, recv, db.world, src_stride, lay.off["flags"], self._guard_stats)
-            # Every rank must take the same decision about a re-match (it is a collective path).  Bits raised BEFORE an
-            # exchange reach every rank with it.  In the all-gather form every rank then runs the same merge on the same
-            # bytes, so the bits the merge itself raises (cross-shard near-ties) are the same everywhere: no collective.
-            # In the all-to-all form each owner merges its own query block: those last bits still take a 4-byte MAX
-            # all-reduce, on the device, stream-ordered - the walk carries the agreed value out with the codes.
-            if owner_blocks:
-                allreduce_max_(self._guard_stats[1:2], force=self.force_sharded)
+            self._merge_shards(lay, owner_blocks, T, aud)
         if self.host_ranks:
             for p_ in ("aud", "txt"):
                 if T[p_ + "_d"] is not None:
@@ -1037,58 +1041,136 @@ class CodeKNN:
             T["gate_tables"] = gtab         # [0], [1]: both modalities' candidates for every (step, previous code)
         return T
 
-    def _merge_mixed(self, recv, src_stride, lay, owner_blocks, d, ix, rk, exact=False):
+    def _layout(self, Q, owner_blocks, mode):
+        """The ExchangeLayout (+ send buffer) of this shape: one per shape, reused by every clip (stream-ordered: the
+        previous clip's exchange has read it)."""
+        parts = tuple(p_ for p_, off in (("aud", MODE_TXT), ("txt", MODE_AUD)) if mode != off)
+        key = (Q, self.db.world if owner_blocks else 1, parts, not self.use_wavvq)
+        if key not in self._layouts:
+            self._layouts[key] = ExchangeLayout(key[0], self.db.K, key[1], parts, key[3], self.db.device)
+        return self._layouts[key]
+
+    def _merge_shards(self, lay, owner_blocks, T, aud):
+        """The sharded step's second half: ONE collective for both modalities (all-to-all when every rank only needs its
+        own clip's rows, all-gather otherwise), then one merge launch per modality into T: min distance, lowest global
+        index among equals, ranks.  The trouble word rides in the blocks (ExchangeLayout "flags"): stamped here, ORed in
+        by the receivers.  aud: the AudioResult of this rank's WavLM sweep (None: wavvq or no audio side)."""
+        db, dev = self.db, self.db.device
+        _lib.call("qpg_flags_stamp", dev, lay.send, lay.nblk, lay.block_bytes, lay.off["flags"], self._guard_stats)
+        recv = exchange_bytes(lay.send, db.world, owner_blocks)
+        src_stride = lay.block_bytes if owner_blocks else lay.send.numel()
+        gathered = False
+        for p_ in lay.parts:
+            d = torch.empty((lay.Qb, db.K), dtype=lay.dtype[p_], device=dev)
+            ix = torch.empty((lay.Qb, db.K), dtype=torch.int32, device=dev)
+            rk = torch.empty((lay.Qb, db.K), dtype=torch.int16, device=dev)
+            wavlm_aud = p_ == "aud" and aud is not None
+            if wavlm_aud and aud.plan.path in ("mixed", "exact"):
+                self._merge_mixed(recv, src_stride, lay, owner_blocks, d, ix, rk, aud.q32, aud.qn2, aud.plan)
+                gathered = True
+            elif lay.dtype[p_] == torch.float64:
+                # (f64 sweep + capped guard per shard: near-ties ACROSS shards / codes are detected here and
+                # re-matched on the exact path; exact integer distances of the wavvq mode need no guard)
+                guard = wavlm_aud and self.tie_eps > 0
+                _lib.call("qpg_merge_select_f64", dev, recv, db.world, src_stride, lay.off[p_ + "_d"],
+                          lay.off[p_ + "_i"], lay.Qb, db.K, float(ABSENT_DIST), d, ix, rk,
+                          float(self.tie_eps) if guard else 0.0, self._guard_stats if guard else None)
+            else:
+                _lib.call("qpg_merge_select_f32", dev, recv, db.world, src_stride,
+                          lay.off[p_ + "_d"], lay.off[p_ + "_i"], lay.Qb, db.K, float(ABSENT_DIST), d, ix, rk)
+            T[p_ + "_d"], T[p_ + "_idx"], T[p_ + "_rank"] = d, ix, rk
+        if not gathered:            # (the mixed merge's prologue ORs the received words in itself)
+            _lib.call("qpg_flags_gather", dev, recv, db.world, src_stride, lay.off["flags"], self._guard_stats)
+        # Every rank must take the same decision about a re-match (it is a collective path).  Bits raised BEFORE an
+        # exchange reach every rank with it.  In the all-gather form every rank then runs the same merge on the same
+        # bytes, so the bits the merge itself raises (cross-shard near-ties) are the same everywhere: no collective.
+        # In the all-to-all form each owner merges its own query block: those last bits still take a 4-byte MAX
+        # all-reduce, on the device, stream-ordered - the walk carries the agreed value out with the codes.
+        if owner_blocks:
+            allreduce_max_(self._guard_stats[1:2], force=self.force_sharded)
+
+    def _merge_mixed(self, recv, src_stride, lay, owner_blocks, d, ix, rk, q32, qn2, plan):
         """Cross-shard merge of audio tables whose comparisons are not all decided by their values:
-        approximate merge + requests, re-evaluation of the requested pairs where the rows live, final merge + ranks.
+        approximate merge + requests, re-evaluation of the requested pairs where the rows live (from this rank's packed
+        queries q32 / qn2), final merge + ranks.  plan: the AudioPlan the tables were made by.
         Request slots are deterministic (qpg_merge_mixed_phase1_f64), so:
           all-gather form (every rank holds every shard's tables and runs the same merge): a shard refines ITS block of
             its OWN phase-1 run - no request exchange; ONE all-gather of the responses.  Two collectives per clip in all.
           all-to-all form (every rank owns one query block): the owner's requests travel to the shards and the responses
             back: two more all-to-alls.
         Mixed-precision tables: band = 2.1 x the sweep's bound, responses = f64 dot-product distances; what those leave
-        within tie_eps raises FLAG_CROSS_SHARD_TIE.  exact=True (f64 tables of the uncapped select): band = tie_eps,
+        within tie_eps raises FLAG_CROSS_SHARD_TIE.  Path "exact" (f64 tables of the uncapped select): band = tie_eps,
         responses in the reference's own arithmetic, request and flag lists sized for the worst case - the cross-shard
         tier 2, which cannot overflow and flags nothing."""
         db, dev = self.db, self.db.device
         W, Qb, K = db.world, lay.Qb, db.K
+        exact = plan.path == "exact"
         if exact:
             Rq, fl_cap, band = K, K * W, float(self.tie_eps)
         else:
             # slots per (query, shard): ~70 / W requests per query are usual with the split-f16 band
             Rq = int(self.mixed_requests) if self.mixed_requests else max(64, 512 // W)
-            fl_cap, band = 1024, (AUDIO_HL_BAND if getattr(self, "_last_audio_hl", False) else AUDIO_MX_BAND)
+            fl_cap, band = 1024, plan.band
         R = Qb * Rq
         req_stride = resp_stride = 8 + 8 * R
-        key = ("_mm_bufs_exact" if exact else "_mm_bufs", W, R)
-        cache = self.__dict__.setdefault("_mm_cache", {})
-        bufs = cache.get(key)
+        key = (exact, W, R)
+        bufs = self._mm_cache.get(key)
         need_ws = int(_lib.load().qpg_merge_mixed_ws_bytes(Qb, K, fl_cap))
         if bufs is None or bufs[2].numel() < need_ws:
-            bufs = cache[key] = (torch.empty((W * req_stride,), dtype=torch.uint8, device=dev),
-                                 torch.empty((W * resp_stride,), dtype=torch.uint8, device=dev),
-                                 torch.empty((need_ws,), dtype=torch.uint8, device=dev))
+            bufs = self._mm_cache[key] = (torch.empty((W * req_stride,), dtype=torch.uint8, device=dev),
+                                          torch.empty((W * resp_stride,), dtype=torch.uint8, device=dev),
+                                          torch.empty((need_ws,), dtype=torch.uint8, device=dev))
         req, resp, ws = bufs
         _lib.call("qpg_merge_mixed_phase1_f64", dev, recv, W, src_stride, lay.off["aud_d"], lay.off["aud_i"], Qb, K,
                   float(ABSENT_DIST), band, R, req, req_stride, ws, ws.numel(), self._guard_stats, fl_cap,
                   lay.off["flags"])
         half = int(db.feature_dtype == "f16")
+        refine = (db.idx_base * db.Ga, db.base, half, db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride,
+                  q32, qn2, db.cn2, resp, resp_stride, int(exact), self._guard_stats, Rq)
         if owner_blocks:
             req_recv = exchange_bytes(req, W, True)
             # block o of req_recv comes from owner o: its queries are rows o*Qb .. of this rank's packed query set
-            _lib.call("qpg_shard_refine_f64", dev, req_recv, W, req_stride, R, Qb, db.idx_base * db.Ga, db.base, half,
-                      db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, self._last_q32, self._last_qn2,
-                      db.cn2, resp, resp_stride, int(exact), self._guard_stats, Rq)
+            _lib.call("qpg_shard_refine_f64", dev, req_recv, W, req_stride, R, Qb, *refine)
             resp_recv = exchange_bytes(resp, W, True)
         else:
             # every rank ran the same phase 1: block `rank` of MY request buffer is what owner(s) would have sent me
             mine = req[db.rank * req_stride:(db.rank + 1) * req_stride]
-            _lib.call("qpg_shard_refine_f64", dev, mine, 1, req_stride, R, 0, db.idx_base * db.Ga, db.base, half,
-                      db.T, db.F, db.aud_t, db.Ga, NUM_AUDIO_FEAT_FRAMES, db.tap_stride, self._last_q32, self._last_qn2,
-                      db.cn2, resp, resp_stride, int(exact), self._guard_stats, Rq)
+            _lib.call("qpg_shard_refine_f64", dev, mine, 1, req_stride, R, 0, *refine)
             resp_recv = exchange_bytes(resp[:resp_stride], W, False)
         _lib.call("qpg_merge_mixed_phase2_f64", dev, recv, W, src_stride, lay.off["aud_i"], Qb, K, float(ABSENT_DIST), ws,
                   ws.numel(), resp_recv, resp_stride, d, ix, rk, self._guard_stats, fl_cap,
                   0.0 if exact else float(self.tie_eps))
+
+    # -- the walk ------------------------------------------------------------------------------------
+    def _seed_phase_tensor(self, seed_phase):
+        if isinstance(seed_phase, torch.Tensor):
+            return seed_phase.to(self.db.device, torch.float32).contiguous()
+        return torch.as_tensor(np.asarray(seed_phase, np.float32), device=self.db.device).contiguous()
+
+    def _launch_walk(self, T, q0, Qt, rows, mode, prefusable, M, steps, seed, sp, outs, chains=None):
+        """The walk over table rows [q0, q0 + Qt): qpg_match_steps (chains None; seed: the seed code) or
+        qpg_match_steps_batch (`chains` independent clips back to back; seed: their i32 seed codes in device-readable
+        memory).  sp: the f32 [8][16] seed phase block(s); outs = (codes, phases, votes, status).  The tables' own gate
+        tables are taken as they are (QPG_MODE_PREFUSED) when they cover exactly these rows and `prefusable`; otherwise
+        the walk fuses the ranks itself into a scratch table of `rows` rows.  Returns the gate tables used."""
+        db, dev = self.db, self.db.device
+        gate = T.get("gate_tables")
+        prefused = prefusable and gate is not None and mode == MODE_AUD_TXT and gate.shape[1] == Qt
+        if not prefused:
+            gate = torch.empty((3, rows, db.K), dtype=torch.int32, device=dev)
+        mode_w = mode | (_lib.QPG_MODE_PREFUSED if prefused else 0)
+        if chains is None and self.serial_walk:
+            mode_w |= _lib.QPG_MODE_SERIAL_WALK
+        a_cidx, a_pslot, a_G = self._audio_grid()
+        tabs = [None if T[k] is None else T[k][q0:q0 + Qt] for k in ("aud_rank", "aud_idx", "txt_rank", "txt_idx")]
+        head = (*tabs, db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G, db.txt_cidx,
+                db.txt_pslot, db.Gt, db.phase, db.Tp, mode_w, M, steps, db.K)
+        guard = self._guard_stats[1:2]
+        if chains is None:
+            _lib.call("qpg_match_steps", dev, *head, seed, sp, gate, *outs, guard)
+        else:
+            _lib.call("qpg_match_steps_batch", dev, *head, chains, seed, sp, gate, *outs, 2, guard)
+        return gate
 
     def walk(self, T, n_windows, window_offset=0, mode=MODE_AUD_TXT, seed_code=None, seed_phase=None, sync=True,
              seed_ptrs=None, out_pin=None, n_chains=1):
@@ -1110,37 +1192,31 @@ class CodeKNN:
         CL = int(n_chains)
         assert CL == 1 or (seed_ptrs is not None and out_pin is not None), "several chains: the graph path only"
         if seed_ptrs is not None:
-            seed_code, sp = 0, int(seed_ptrs[1])
-        elif seed_code is None:
-            seed_code, seed_phase = self.init_code_phase()
-        if seed_ptrs is not None:
-            pass
-        elif isinstance(seed_phase, torch.Tensor):
-            sp = seed_phase.to(dev, torch.float32).contiguous()
+            sp = int(seed_ptrs[1])
         else:
-            sp = torch.as_tensor(np.asarray(seed_phase, np.float32), device=dev).contiguous()
+            if seed_code is None:
+                seed_code, seed_phase = self.init_code_phase()
+            sp = self._seed_phase_tensor(seed_phase)
         # codes | votes | status (2) in ONE buffer: the integer results leave in a single D2H copy, no gather kernel
         # before it.  status[0] = an absent code won a rank fusion, status[1] = the sweeps' / selects' trouble word
         # (copied by the walk's last kernel from _guard_stats[1]): a clip whose word is not 0 is never returned.
         n_c, n_v = M * num_frames_code, M * steps
         host = sync is True or sync == "ints"
-        if out_pin is not None:
-            assert not host and out_pin.numel() >= CL * (n_c + n_v + 2)
-            base = out_pin.data_ptr()
-            out_codes, out_vote, status = base, base + 4 * CL * n_c, base + 4 * CL * (n_c + n_v)
-        elif host:
-            # pinned (device-visible) host memory, one buffer per clip length: safe to reuse because this call does
-            # not return before the stream has drained and the values have been copied out of it
-            pins = self.__dict__.setdefault("_pinned_ints", {})
-            pin = pins.get(M)
+        if out_pin is not None or host:
+            pin = out_pin
             if pin is None:
-                pin = pins[M] = torch.empty((n_c + n_v + 2,), dtype=torch.int32).pin_memory()
+                # pinned (device-visible) host memory, one buffer per clip length: safe to reuse because this call does
+                # not return before the stream has drained and the values have been copied out of it
+                if M not in self._pinned_ints:
+                    self._pinned_ints[M] = torch.empty((n_c + n_v + 2,), dtype=torch.int32).pin_memory()
+                pin = self._pinned_ints[M]
+                # every word is a sentinel until the walk has written it; the status word is the walk's LAST store (behind
+                # a system-scope fence), the others are checked as well before the buffer is copied (_wait_pinned)
+                pin_np = pin.numpy()
+                pin_np.fill(_PIN_SENTINEL)
+            assert not (host and out_pin is not None) and pin.numel() >= CL * (n_c + n_v + 2)
             base = pin.data_ptr()
-            out_codes, out_vote, status = base, base + 4 * n_c, base + 4 * (n_c + n_v)
-            pin_np = pin.numpy()
-            # every word is a sentinel until the walk has written it; the status word is the walk's LAST store (behind a
-            # system-scope fence), the others are checked as well before the buffer is copied (_wait_pinned)
-            pin_np.fill(_PIN_SENTINEL)
+            out_codes, out_vote, status = base, base + 4 * CL * n_c, base + 4 * CL * (n_c + n_v)
         else:
             ints_d = torch.empty((n_c + n_v + 2,), dtype=torch.int32, device=dev)
             out_codes = ints_d[:n_c].view(M, num_frames_code)
@@ -1148,28 +1224,13 @@ class CodeKNN:
             status = ints_d[n_c + n_v:]                                  # always written by the walk kernels
         out_phase = torch.empty((CL * M, steps, 8, 16), dtype=torch.float32, device=dev)
         q0 = window_offset * steps
-        gate = T.get("gate_tables")
-        prefused = (gate is not None and mode == MODE_AUD_TXT and q0 == 0 and gate.shape[1] == CL * M * steps and
-                    M > 0 and not self.serial_walk)
-        if not prefused:
-            gate = torch.empty((3, max(CL * M, 1) * steps, db.K), dtype=torch.int32, device=dev)
-        mode_w = mode | (_lib.QPG_MODE_PREFUSED if prefused else 0)
-
-        def sl(t):
-            return None if t is None else t[q0:q0 + CL * M * steps]
-        a_cidx, a_pslot, a_G = self._audio_grid()
-        if seed_ptrs is not None:
-            # one chain through the batch entry: its seed code is read from memory by the kernels
-            _lib.call("qpg_match_steps_batch", dev, sl(T["aud_rank"]), sl(T["aud_idx"]), sl(T["txt_rank"]),
-                      sl(T["txt_idx"]), db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G,
-                      db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp, mode_w, M, steps, db.K, CL, int(seed_ptrs[0]), sp,
-                      gate, out_codes, out_phase, out_vote, status, 2, self._guard_stats[1:2])
+        outs = (out_codes, out_phase, out_vote, status)
+        prefusable = q0 == 0 and M > 0 and not self.serial_walk
+        if seed_ptrs is not None:           # through the batch entry: the seed codes are read from memory by the kernels
+            self._launch_walk(T, q0, CL * M * steps, max(CL * M, 1) * steps, mode, prefusable, M, steps,
+                              int(seed_ptrs[0]), sp, outs, chains=CL)
         else:
-            _lib.call("qpg_match_steps", dev, sl(T["aud_rank"]), sl(T["aud_idx"]), sl(T["txt_rank"]), sl(T["txt_idx"]),
-                      db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G,
-                      db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp,
-                      mode_w | (_lib.QPG_MODE_SERIAL_WALK if self.serial_walk else 0), M, steps, db.K, int(seed_code), sp,
-                      gate, out_codes, out_phase, out_vote, status, self._guard_stats[1:2])
+            self._launch_walk(T, q0, M * steps, max(M, 1) * steps, mode, prefusable, M, steps, int(seed_code), sp, outs)
         if out_pin is not None:
             return out_codes, out_phase, out_vote, status
         if not host:
@@ -1199,10 +1260,7 @@ class CodeKNN:
         if seeds.shape[0] != CL or (seeds < 0).any() or (seeds >= db.K).any():
             raise ValueError("walk_batch: one seed code in [0, %d) per clip" % db.K)
         sc = torch.as_tensor(seeds.astype(np.int32), device=dev)
-        if isinstance(seed_phases, torch.Tensor):
-            sp = seed_phases.to(dev, torch.float32).contiguous()
-        else:
-            sp = torch.as_tensor(np.asarray(seed_phases, np.float32), device=dev).contiguous()
+        sp = self._seed_phase_tensor(seed_phases)
         if sp.numel() != CL * 128:
             raise ValueError("walk_batch: seed_phases must hold [n_clips][8][16] floats")
         n_c, n_v = M * num_frames_code, M * steps
@@ -1211,18 +1269,8 @@ class CodeKNN:
         votes_d = torch.empty((CL, M, steps), dtype=torch.int32, device=dev)
         out_phase = torch.empty((CL, M, steps, 8, 16), dtype=torch.float32, device=dev)
         Qt = CL * M * steps
-        gate = T.get("gate_tables")
-        prefused = gate is not None and mode == MODE_AUD_TXT and gate.shape[1] == Qt
-        if not prefused:
-            gate = torch.empty((3, Qt, db.K), dtype=torch.int32, device=dev)
-        a_cidx, a_pslot, a_G = self._audio_grid()
-
-        def sl(t):
-            return None if t is None else t[:Qt]
-        _lib.call("qpg_match_steps_batch", dev, sl(T["aud_rank"]), sl(T["aud_idx"]), sl(T["txt_rank"]), sl(T["txt_idx"]),
-                  db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G,
-                  db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp, mode | (_lib.QPG_MODE_PREFUSED if prefused else 0), M,
-                  steps, db.K, CL, sc, sp, gate, codes_d, out_phase, votes_d, status_d, 2, self._guard_stats[1:2])
+        gate = self._launch_walk(T, 0, Qt, Qt, mode, True, M, steps, sc, sp, (codes_d, out_phase, votes_d, status_d),
+                                 chains=CL)
         self._last_ints = torch.cat((codes_d.view(CL, n_c), votes_d.view(CL, n_v), status_d), dim=1)
         self._last_gate_tables = gate                       # (tests compare the candidate tables of the two fusion paths)
         return codes_d, out_phase, votes_d
@@ -1252,6 +1300,13 @@ class CodeKNN:
         return ClipGraph(self, n_windows, mode, n_sweep_windows or n_windows * n_clips, window_offset, audio, context,
                          owner_blocks, n_clips, encoder, encode_input, encode_precision, sweep_signal, doorbell)
 
+    def _tables_and_walk(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables,
+                         for_walk=False):
+        T = self.sweep_tables(test_interp, test_context, n_windows, mode, for_walk=for_walk)
+        if return_tables:
+            self.tables = T
+        return self.walk(T, n_windows, 0, mode, seed_code, seed_phase)
+
     def match_clip(self, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, seed_code=None,
                    seed_phase=None, return_tables=False):
         """All windows of one clip: two batched sweeps + rank kernels + one device-side tail walk.
@@ -1263,37 +1318,32 @@ class CodeKNN:
         if n_windows == 0:                          # an empty clip (the reference's loop body never runs, :785)
             return (np.zeros((0, num_frames_code), np.int64), np.zeros((0, self.n_steps(), 8, 16), np.float32),
                     np.zeros((0, self.n_steps()), np.int32))
-        test_interp = test_interp.contiguous()
+        clip = (test_interp.contiguous(), test_context, n_windows, mode, seed_code, seed_phase, return_tables)
         try:
-            T = self.sweep_tables(test_interp, test_context, n_windows, mode, for_walk=not return_tables)
-            if return_tables:
-                self.tables = T
-            return self.walk(T, n_windows, 0, mode, seed_code, seed_phase)
+            return self._tables_and_walk(*clip, for_walk=not return_tables)
         except GuardOverflow as e:
             if self.audio_precision == "exact":
                 self.clear_flags()          # (the sticky word must not poison the clips after this one)
                 raise RuntimeError("the uncapped path raised flags 0x%x: this is a bug" % e.flags)
-            return self.rematch(e.flags, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
+            return self.rematch(e.flags, *clip)
 
     def rematch(self, flags, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False):
         """The clip again on a path that cannot raise `flags`: only the text prefilter overflowed (FLAG_TEXT_OVERFLOW alone)
         -> the same audio path with the text side on the exact-order sweep; anything else -> audio_precision "exact"
         (f64 sweep + uncapped guard, which also takes the exact-order text sweep).  Clears the trouble word."""
+        clip = (test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
         if flags == FLAG_TEXT_OVERFLOW and self.text_kernel == "mfma":
             self.clear_flags()
             self.fallbacks += 1
-            self.text_fallbacks = getattr(self, "text_fallbacks", 0) + 1
+            self.text_fallbacks += 1
             self.text_kernel = "valu"
             try:
-                T = self.sweep_tables(test_interp, test_context, n_windows, mode)
-                if return_tables:
-                    self.tables = T
-                return self.walk(T, n_windows, 0, mode, seed_code, seed_phase)
-            except GuardOverflow as e2:          # the audio side of this clip is in trouble as well
-                return self.rematch_exact(test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
+                return self._tables_and_walk(*clip)
+            except GuardOverflow:               # the audio side of this clip is in trouble as well
+                return self.rematch_exact(*clip)
             finally:
                 self.text_kernel = "mfma"
-        return self.rematch_exact(test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
+        return self.rematch_exact(*clip)
 
     def rematch_exact(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False):
         """The clip again with audio_precision "exact" (f64 sweep + uncapped guard); clears the trouble word."""
@@ -1302,12 +1352,11 @@ class CodeKNN:
         self.audio_precision = "exact"
         self.fallbacks += 1
         try:
-            T = self.sweep_tables(test_interp, test_context, n_windows, mode)
-            if return_tables:
-                self.tables = T
-            return self.walk(T, n_windows, 0, mode, seed_code, seed_phase)
+            return self._tables_and_walk(test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
         finally:
             self.audio_precision = prev
+
+
 
 
 def predict_code_from_audio(db, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, rng=None):

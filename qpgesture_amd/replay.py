@@ -176,18 +176,17 @@ class ClipGraph:
             main = torch.cuda.current_stream(dev)
             if self._doorbell:                   # (first node: everything below is ordered behind it)
                 _lib.call("qpg_doorbell_wait", dev, self._db_cnt, self._db_go.data_ptr(), 2000)
+            behind_sweep = None                  # (what goes out directly behind the audio sweep kernel)
             if self.enc is not None:
                 if enc_at == "start" or self.mode == MODE_TXT or knn.use_wavvq:
                     encode_leg()
                 else:
-                    knn.after_sweep = encode_leg
+                    behind_sweep = encode_leg
             elif self._sweep_flag is not None:
-                knn.after_sweep = lambda: _lib.call("qpg_signal_i32", dev, self._sweep_flag.data_ptr(), 1)
-            try:
-                T = knn.sweep_tables(self.audio, self.context, self._n_sweep, self.mode, owner_blocks=self.owner_blocks,
-                                     for_walk=True)
-            finally:
-                knn.after_sweep = None
+                def behind_sweep():
+                    _lib.call("qpg_signal_i32", dev, self._sweep_flag.data_ptr(), 1)
+            T = knn.sweep_tables(self.audio, self.context, self._n_sweep, self.mode, owner_blocks=self.owner_blocks,
+                                 for_walk=True, after_sweep=behind_sweep)
             if self.enc is not None:
                 main.wait_event(self._enc_done)
             return knn.walk(T, self.M, self._off, self.mode, sync=False, seed_ptrs=ptrs, out_pin=self._pin,

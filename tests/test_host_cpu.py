@@ -735,3 +735,152 @@ def test_bench_dump_outputs_writes_float64(tmp_path):
     assert os.listdir(tmp_path / "two") == ["codes_rank1.npy"]
     with pytest.raises(ValueError):
         b.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((b.DUMP_LIMIT_BYTES // 8 + 1,), np.float32)}, 1, 0)
+
+
+# ---- the step plan (code_knn.plan_audio / plan_text / plan_step): which kernels a call takes, decided on plain values ----
+_HL, _MX = ck.AUDIO_HL_BAND, ck.AUDIO_MX_BAND
+_ONE_GPU = dict(n_local=2048, N=2048, world=1, K=512, Ga=26, F=1024, Dt=384)
+_SHARD = dict(_ONE_GPU, n_local=1024, world=2)            # one of two row shards
+
+
+def _step(db=_ONE_GPU, M=3, steps=8, mode=ck.MODE_AUD_TXT, for_walk=True, owner_blocks=False, **knobs):
+    p = ck.plan_step(ck.Knobs(**knobs), ck.DBFacts(**db), M, steps, mode, for_walk, owner_blocks)
+    return (None if p.audio is None else tuple(p.audio),) + tuple(p[1:])
+
+
+def test_step_plan_table():
+    """A literal table of plans, written from the conditions of the kernels' paths (not produced by the functions):
+    (audio = (path, sweep kernel, band, cut, ranks fused) | None, text, sharded, exchange, one-launch pack, split rank
+    fusion, overlap, order)."""
+    hl1 = ("mixed", "hl", _HL, 1, True)
+    f16 = dict(_ONE_GPU, feature_dtype="f16", hl_planes=1)
+    table = [
+        # a one-GPU default clip into the walk; the same with return_tables (no cut, no split fusion)
+        (dict(), (hl1, "mfma", False, None, True, True, True, "audio_first")),
+        (dict(for_walk=False), (("mixed", "hl", _HL, 0, True), "mfma", False, None, True, False, True, "audio_first")),
+        (dict(mode=ck.MODE_AUD), (("mixed", "hl", _HL, 2, True), None, False, None, False, False, False, None)),
+        (dict(mode=ck.MODE_TXT), (None, "mfma", False, None, False, False, False, None)),
+        # each knob alone
+        (dict(audio_precision="f64"), (("guarded", "f64", 0.0, 0, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(audio_precision="exact"),
+         (("exact", "f64", 0.0, 0, True), "valu", False, None, False, True, True, "text_after_sweep")),
+        (dict(audio_kernel="mx"), (("mixed", "mx", _MX, 1, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(text_kernel="valu"), (hl1, "valu", False, None, False, True, True, "text_after_sweep")),
+        (dict(fused_pack=False), (hl1, "mfma", False, None, False, True, True, "audio_first")),
+        (dict(split_fuse=False), (hl1, "mfma", False, None, True, False, True, "audio_first")),
+        (dict(rank_cut=False), (("mixed", "hl", _HL, 0, True), "mfma", False, None, True, True, True, "audio_first")),
+        (dict(mixed_single_launch=True), (("mixed", "hl", _HL, 0, True), "mfma", False, None, True, True, True, "audio_first")),
+        (dict(tie_eps=0.0), (("plain", "f64", 0.0, 0, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(host_ranks=True), (("mixed", "hl", _HL, 0, True), "mfma", False, None, True, False, True, "audio_first")),
+        # the five schedules of test_knn_pred_vs_reference_golden: auto, text_after_sweep, text_first, audio_first, one_stream
+        (dict(audio_first=None), (hl1, "mfma", False, None, True, True, True, "audio_first")),
+        (dict(text_after_sweep=True, audio_first=False), (hl1, "mfma", False, None, True, True, True, "text_after_sweep")),
+        (dict(text_after_sweep=False, audio_first=False), (hl1, "mfma", False, None, True, True, True, "text_first")),
+        (dict(text_after_sweep=False, audio_first=True), (hl1, "mfma", False, None, True, True, True, "audio_first")),
+        (dict(overlap_sweeps=False), (hl1, "mfma", False, None, False, True, False, None)),
+        # facts of the database
+        (dict(db=f16), (("mixed", "hl1", _HL, 1, True), "mfma", False, None, True, True, True, "audio_first")),
+        (dict(db=f16, audio_kernel="mx"), (("mixed", "mx_h", _MX, 1, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=f16, audio_precision="f64"),
+         (("guarded", "f64_h", 0.0, 0, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=dict(_ONE_GPU, hl_bound_ok=False)),
+         (("guarded", "f64", 0.0, 0, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=dict(_ONE_GPU, hl_bound_ok=False, has_hl_image=False, has_txt_sorted=False)),   # as GestureDB leaves it
+         (("guarded", "f64", 0.0, 0, True), "valu", False, None, False, True, True, "text_after_sweep")),
+        (dict(db=dict(_ONE_GPU, has_hl_image=False)),
+         (("mixed", "mx", _MX, 1, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=dict(_ONE_GPU, K=1024)), (("guarded", "f64", 0.0, 0, True), "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=dict(_ONE_GPU, K=520)), (("guarded", "f64", 0.0, 0, True), "mfma", False, None, False, False, True, "audio_first")),
+        (dict(db=dict(_ONE_GPU, Dt=320)), (hl1, "mfma", False, None, False, True, True, "audio_first")),
+        (dict(db=dict(_SHARD, n_local=0, has_hl_image=False, has_txt_sorted=False)),              # an empty shard
+         (("plain", "f64", 0.0, 0, False), "valu", True, "all_gather", False, False, True, "text_after_sweep")),
+        # the wavvq sweep has one path, takes no pack and is never waited for by the text side
+        (dict(use_wavvq=True), (None, "mfma", False, None, False, True, True, "audio_first")),
+        (dict(use_wavvq=True, text_after_sweep=True, audio_first=False), (None, "mfma", False, None, False, True, True, "text_first")),
+        # split fusion up to split_fuse_max_steps = 256 steps: 32 x 8 = 256, 33 x 8 = 264
+        (dict(M=32), (hl1, "mfma", False, None, True, True, True, "audio_first")),
+        (dict(M=33), (hl1, "mfma", False, None, True, False, True, "audio_first")),
+        # row shards: 2e-9 * Q * 1024 * 26 * 6 * 1024 GFLOP per rank = 7.85 (Q = 24), 31.4 (Q = 96) against 20
+        (dict(db=_SHARD), (("guarded", "f64", 0.0, 0, False), "mfma", True, "all_gather", False, False, True, "audio_first")),
+        (dict(db=_SHARD, M=12), (("mixed", "hl", _HL, 0, False), "mfma", True, "all_gather", True, False, True, "audio_first")),
+        (dict(db=_SHARD, M=12, owner_blocks=True),
+         (("mixed", "hl", _HL, 0, False), "mfma", True, "all_to_all", True, False, True, "audio_first")),
+        (dict(db=_SHARD, M=12, sharded_mixed=False),
+         (("guarded", "f64", 0.0, 0, False), "mfma", True, "all_gather", False, False, True, "audio_first")),
+        (dict(db=_SHARD, M=12, audio_kernel="mx"),
+         (("mixed", "mx", _MX, 0, False), "mfma", True, "all_gather", False, False, True, "audio_first")),
+        (dict(db=_SHARD, M=12, audio_precision="exact", owner_blocks=True),
+         (("exact", "f64", 0.0, 0, False), "valu", True, "all_to_all", False, False, True, "text_after_sweep")),
+        # force_sharded on one GPU: 2e-9 * 24 * 2048 * 26 * 6 * 1024 = 15.7 GFLOP
+        (dict(force_sharded=True), (("guarded", "f64", 0.0, 0, False), "mfma", True, "all_gather", False, False, True, "audio_first")),
+        (dict(force_sharded=True, sharded_mixed_min_gflop=0.0, owner_blocks=True),
+         (("mixed", "hl", _HL, 0, False), "mfma", True, "all_to_all", True, False, True, "audio_first")),
+        (dict(force_sharded=True, mode=ck.MODE_AUD, sharded_mixed_min_gflop=0.0),
+         (("mixed", "hl", _HL, 0, False), None, True, "all_gather", False, False, False, None)),
+    ]
+    for kw, want in table:
+        assert _step(**kw) == want, kw
+    # the stand-alone sweeps (search_*_cands, tests): no ranks wanted -> nothing fused, the f64 sweep + guard
+    kn, db = ck.Knobs(), ck.DBFacts(**_ONE_GPU)
+    assert tuple(ck.plan_audio(kn, db, 1)) == ("guarded", "f64", 0.0, 0, False)
+    assert tuple(ck.plan_audio(kn, db, 24, want_rank=True, cut_top_n=2)) == ("mixed", "hl", _HL, 2, True)
+    assert tuple(ck.plan_audio(kn, db, 24, want_rank=True, cut_top_n=3)) == ("mixed", "hl", _HL, 0, True)
+    assert ck.plan_text(kn, db, 1) == "mfma" and ck.plan_text(kn, db, 0) == "valu"
+    assert ck.plan_text(kn, db, 1, reduce=False) == "valu" and ck.plan_text(kn, db, 1, reduce=False, out_given=True) == "mfma"
+    assert ck.plan_text(kn, ck.DBFacts(**_SHARD), 1) == "valu"
+
+
+def test_step_plan_hands_each_side_its_own_plan():
+    """For every combination of the boolean knobs, the audio / text parts of the step's plan are what plan_audio /
+    plan_text give for the arguments sweep_tables passes to the two sides - and the one-launch pack is only planned
+    where the audio side takes the split-f16 sweep and the text side the prefilter that read the pack's images."""
+    import itertools
+    bools = ["overlap_sweeps", "text_after_sweep", "fused_pack", "rank_cut", "split_fuse", "host_ranks", "use_wavvq",
+             "force_sharded", "sharded_mixed", "mixed_single_launch"]
+    n = 0
+    for vals in itertools.product((False, True), repeat=len(bools)):
+        for prec, af, db, for_walk in itertools.product(("mixed", "exact"), (None, False), (_ONE_GPU, _SHARD), (False, True)):
+            kn = ck.Knobs(audio_precision=prec, audio_first=af, sharded_mixed_min_gflop=0.0, **dict(zip(bools, vals)))
+            facts = ck.DBFacts(**db)
+            sharded = facts.world > 1 or kn.force_sharded
+            for mode in (ck.MODE_AUD_TXT, ck.MODE_AUD, ck.MODE_TXT):
+                p = ck.plan_step(kn, facts, 3, 8, mode, for_walk)
+                cut = 0
+                if for_walk and kn.rank_cut and not sharded and not kn.use_wavvq and not kn.host_ranks:
+                    cut = 1 if mode == ck.MODE_AUD_TXT else 2
+                want_a = None if (mode == ck.MODE_TXT or kn.use_wavvq) else ck.plan_audio(
+                    kn, facts, 24, want_rank=not sharded, reduce=not sharded, out_given=sharded, cut_top_n=cut)
+                want_t = None if mode == ck.MODE_AUD else ck.plan_text(kn, facts, 24, reduce=not sharded, out_given=sharded)
+                assert p.audio == want_a and p.text == want_t and p.sharded == sharded
+                assert p.overlap == (p.order is not None) == (mode == ck.MODE_AUD_TXT and kn.overlap_sweeps)
+                if p.clip_pack:
+                    assert p.audio.kernel == "hl" and p.text == "mfma" and p.overlap
+                n += 1
+    assert n == 2 ** len(bools) * 16 * 3
+
+
+def test_matcher_declares_its_state_and_its_knobs_feed_the_plan():
+    """CodeKNN hands the plan functions its own knobs, field by field, with the defaults Knobs() states; every member
+    it uses exists after __init__ (no member appears on first use), and no method decides by a `_last_*` diagnostic."""
+    import re
+    import types
+    import torch
+    fake = types.SimpleNamespace(step_sz=6, T=180, N=4, device=torch.device("cpu"), n_local=4, world=1, K=512, Ga=26, F=8,
+                                 Dt=384, feature_dtype="f32", hl_bound_ok=True, hl_image=None, txt_sorted=object(), hl_planes=2)
+    knn = ck.CodeKNN(fake)
+    if "QPG_FUSED_PACK" not in os.environ and "QPG_RANK_CUT" not in os.environ:
+        assert knn._knobs() == ck.Knobs()
+    for i, f in enumerate(ck.Knobs._fields):
+        setattr(knn, f, "knob%d" % i)
+    assert knn._knobs() == ck.Knobs(*["knob%d" % i for i in range(len(ck.Knobs._fields))])
+    assert knn._facts() == ck.DBFacts(4, 4, 1, 512, 26, 8, 384, "f32", True, False, True, 2)
+    src = open(ck.__file__).read()
+    body = src[src.index("class CodeKNN"):]
+    assert "self.__dict__" not in body and "getattr(self," not in body
+    for gone in ("_hl_plan", "_want_sweep_event", "_sweep_done"):
+        assert gone not in src
+    used = set(re.findall(r"self\.(_?[a-z]\w*)\b(?!\()", body))
+    methods = set(re.findall(r"def (\w+)\(", body))
+    assert not {u for u in used if u not in methods and not hasattr(knn, u)}
+    reads = [l.strip() for l in body.splitlines() if "self._last_" in l.rsplit(" = ", 1)[-1]]
+    assert reads == ["ws, Q = self._mix_ws, self._last_mix_Q"]          # (tier1_list_lengths: itself a diagnostic)
