@@ -53,6 +53,11 @@ int qpg_ctx_destroy(qpg_ctx* ctx);
  *                                   deduplicated by the previous winner (default 1 = always; 0 = never: round 4's plain
  *                                   table, bit-identical results - the tests walk on both). */
 #define QPG_OPT_GATE_DEDUP_FROM_CHAINS 0
+/*   QPG_OPT_TAKES_STAGES            which of qpg_match_steps_takes' own kernels a call launches: bit 0 = step 0 of every
+ *                                   take, bit 1 = the chase, bit 2 = the epilogue (default 7 = all).  Measurement only
+ *                                   (tools/bench_takes.py times each kernel between two HIP events): a stage that is
+ *                                   left out reads what an earlier full call left in the same workspace. */
+#define QPG_OPT_TAKES_STAGES 1
 #define QPG_OPT_COUNT 4
 int qpg_ctx_set_option(qpg_ctx* ctx, int option, int value);
 int qpg_ctx_get_option(qpg_ctx* ctx, int option, int* value);
@@ -534,6 +539,28 @@ int qpg_match_steps_batch(qpg_ctx*, void* stream, const int16_t* aud_rank, const
                           int n_chains, const int32_t* seed_codes, const float* seed_phase, int32_t* gate_tables,
                           int32_t* out_codes, float* out_phase, int32_t* out_vote, int32_t* out_status,
                           int64_t status_stride, const int32_t* guard_flags);
+/* Several TAKES of ONE clip: the clip's tables (Q = M x steps rows, as for qpg_match_steps) walked from n_takes seeds in
+ * one set of launches.  Nothing in front of the walk reads the seed, and of the walk only a take's first step does: the
+ * rank fusion (unless QPG_MODE_PREFUSED) and the gate table run ONCE, through qpg_match_steps' kernels (the same bits as a
+ * one-take call); then one kernel evaluates step 0 of every take, one chases all takes (64 per block: a window's gate
+ * table is staged into LDS once per block, one lane per take) and one writes the results (a block per take).
+ *   n_takes 1 .. QPG_TAKES_MAX; seed_codes [dev-readable] i32 [n_takes], every one in [0, K) (the caller checks);
+ *   seed_phase [dev-readable] f32 [n_takes][8][16]; gate_tables [dev] i32 [3][Q][K] as for ONE clip;
+ *   out_codes i32 [n_takes][M][30]; out_phase f32 [n_takes][M][steps][8][16]; out_vote i32 [n_takes][M][steps];
+ *   take t's status pair at out_status + t x status_stride (>= 2), written last behind a system-scope fence;
+ *   workspace [dev]: qpg_match_steps_takes_ws_bytes(n_takes, M, steps) bytes (the takes' trails of states).
+ * mode: the three modality modes and QPG_MODE_PREFUSED as for qpg_match_steps.  Where the tabulated walk does not apply
+ * (QPG_MODE_SERIAL_WALK, a geometry the tabulation refuses) the call returns QPG_EUNSUP before launching anything: the
+ * caller walks the takes one at a time. */
+#define QPG_TAKES_MAX 65536
+size_t qpg_match_steps_takes_ws_bytes(int n_takes, int M, int steps);
+int qpg_match_steps_takes(qpg_ctx*, void* stream, const int16_t* aud_rank, const int32_t* aud_idx, const int16_t* txt_rank,
+                          const int32_t* txt_idx, const int16_t* pos_rank, const int16_t* freq_rank, const int32_t* code,
+                          int code_ld, const int32_t* aud_cidx, const int32_t* aud_pslot, int Ga, const int32_t* txt_cidx,
+                          const int32_t* txt_pslot, int Gt, const float* phase, int Tp, int mode, int M, int steps, int K,
+                          int n_takes, const int32_t* seed_codes, const float* seed_phase, int32_t* gate_tables,
+                          int32_t* out_codes, float* out_phase, int32_t* out_vote, int32_t* out_status,
+                          int64_t status_stride, const int32_t* guard_flags, void* workspace, size_t workspace_bytes);
 /* One modality's half of the rank fusion in front of the walk (GestureKNN.py:540-545 + :574-576 for the audio order,
  * :553-555 for the text order - two independent argsorts): T[q][p] = idx[q][argmin_c (pos_rank[p][c] + 0.05 freq_rank[c])
  * + rank[q][c]] (f64, that order of operations; lowest code among equal scores).  rank [dev] i16 [Q][K] (a permutation per

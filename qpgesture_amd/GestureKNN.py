@@ -12,7 +12,11 @@ with / without text), --seed (default 123456 as :19; in wavvq modes that seed dr
 phase slice in the reference as well), --tie_rule (how EQUAL values are ranked - code frequencies, and the per-code
 audio / text minima, which tie exactly on real text data where silent frames share one embedding: `numpy` = the
 reference's own `argsort().argsort()` call on the host (NumPy's unstable sort, like the reference), `stable` = lowest
-code first, deterministic, ranks taken on the device).
+code first, deterministic, ranks taken on the device), --n_takes S (default 1: the output file is the reference's, byte
+for byte; S > 1: the clip is matched as with 1, then S - 1 further seeds are drawn from np.random - what S - 1 further runs
+of the reference's loop would draw - and all S takes are walked from the tables that produced `knn_pred`, in one set of
+launches (CodeKNN.walk_takes); the file gains `knn_pred_takes` int64 (S, M, 30) with take 0 == `knn_pred`,
+`take_seed_codes` (S,) and `take_first_shared_code` (S,): from which code on a take repeats an earlier one).
 """
 import argparse
 import os
@@ -51,6 +55,10 @@ def build_parser():
                         "undecided comparison (same output); f64: the f64 matrix-core sweep; exact: f64 sweep + the uncapped "
                         "near-tie guard.  A clip on which a capped guard of mixed / f64 raises its trouble word is "
                         "re-matched on `exact` automatically: unguarded codes are never written")
+    p.add_argument('--n_takes', type=int, default=1,
+                   help="matched clips to write, each from its own init_code_phase() draw (take 0 is knn_pred); seeds that "
+                        "lead the walk into the same state give the same gesture from there on: the number of DISTINCT takes "
+                        "is printed")
     p.add_argument('--db_cache', choices=["auto", "off", "refresh"], default="auto",
                    help="prepared-database cache (qpgesture_amd/db_cache.py): the device-resident database this command "
                         "builds from the five database-side files is written once, keyed by their paths, sizes and mtimes, "
@@ -127,14 +135,33 @@ def main_codebook(args, maxFrames=0):
     # share one embedding); continuous features do not.
     pred_seqs, _, _ = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
                                      return_tables=True)                           # (re-matches on the uncapped path if flagged)
+    n_takes = int(getattr(args, "n_takes", 1))
+    if n_takes < 1:
+        raise ValueError("--n_takes must be >= 1")
     if args.tie_rule == "numpy" and bool(_tables_have_exact_ties(knn.tables)):
         knn.host_ranks = True
-        pred_seqs, _, _ = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase)
+        # (several takes: the host-ranked tables are kept - the takes are walked from the tables that produced knn_pred)
+        pred_seqs, _, _ = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
+                                         return_tables=n_takes > 1)
+    takes_out = {}
+    if n_takes > 1:
+        from . import takes
+        more = [knn.init_code_phase() for _ in range(n_takes - 1)]                 # (np.random, like the first)
+        seed_codes = np.array([seed_code] + [m[0] for m in more], np.int64)
+        seed_phases = np.stack([np.asarray(seed_phase, np.float32)] + [m[1] for m in more])
+        if n_test_seq:
+            tcodes, _, _ = knn.walk_takes(knn.tables, n_test_seq, seed_codes, seed_phases, mode=mode)
+        else:
+            tcodes = np.zeros((n_takes, 0, pred_seqs.shape[1]), np.int64)
+        assert np.array_equal(tcodes[0], pred_seqs), "take 0 must be knn_pred"
+        takes_out = dict(knn_pred_takes=tcodes, take_seed_codes=seed_codes,
+                         take_first_shared_code=takes.first_shared_code(tcodes))
+        print('takes: %d requested, n_distinct %d' % (n_takes, takes.n_distinct(tcodes)))
     t2 = time.time()
     if knn.fallbacks:
         print('near-tie guard: a capped re-evaluation list overflowed; the clip was re-matched on the uncapped path')
     print(pred_seqs.shape)
-    np.savez_compressed(args.out_knn_filename, knn_pred=pred_seqs)               # :845
+    np.savez_compressed(args.out_knn_filename, knn_pred=pred_seqs, **takes_out)  # :845
     print('load+prepare %.2fs%s, match %.4fs (%.0f frames/s)' % (t1 - t0, ' (prepared-database cache)' if from_cache else '',
                                                                    t2 - t1, 240 * n_test_seq / (t2 - t1)))
     if cpath is not None and not from_cache:

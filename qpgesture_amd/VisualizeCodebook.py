@@ -7,6 +7,10 @@
                      then (make_bvh_GENEA2020_BT's own arithmetic, process_bvh.py:57-76, on the device) the ZXY Euler
                      channel table <prefix>_euler.npy and a minimal <prefix>_generated.bvh carrying it
                      (--smoothing = its Savitzky-Golay option).
+                     --takes all | <index> (additive; GestureKNN --n_takes wrote `knn_pred_takes`): every selected take is
+                     decoded in ONE batched pass (zs = one LongTensor (S, 30 M)) and written as generate<prefix>_take<k>.npy,
+                     code<prefix>_take<k>.npy, <prefix>_take<k>_euler.npy, <prefix>_take<k>_generated.bvh; the Euler step
+                     and the smoothing run per take (a smoothing window never crosses from one take into the next).
 
 Same flags as codebook/configs/parse_args.py:4-18.  The pymo inverse pipeline (the recorded skeleton) and mp4
 rendering stay out of scope (see qpgesture_amd/bvh.py).
@@ -34,7 +38,31 @@ def build_parser():
     p.add_argument('--signature_out', type=str, default='./output/code.npz')      # additive
     p.add_argument('--smoothing', action='store_true')                            # additive: process_bvh.py:62-68
     p.add_argument('--no_bvh', action='store_true')                               # additive: stop after the .npy files
+    p.add_argument('--takes', type=parse_takes, default=None)                      # additive: "all" or a take's index
     return p
+
+
+def parse_takes(text):
+    """--takes: "all", or the index of one take (>= 0)."""
+    if text == "all":
+        return "all"
+    try:
+        k = int(text)
+    except ValueError:
+        k = -1
+    if k < 0:
+        raise argparse.ArgumentTypeError("--takes wants 'all' or a take's index (>= 0), got %r" % (text,))
+    return k
+
+
+def select_takes(takes_codes, which):
+    """(indices, codes [S', M, 30]) of `knn_pred_takes` for --takes `which`."""
+    n = takes_codes.shape[0]
+    if which == "all":
+        return list(range(n)), takes_codes
+    if which >= n:
+        raise IndexError("--takes %d: the file holds %d takes" % (which, n))
+    return [which], takes_codes[which:which + 1]
 
 
 def _model(cfg, model_path, gpu):
@@ -57,6 +85,31 @@ def main(argv=None):
         os.makedirs(os.path.dirname(os.path.abspath(args.signature_out)), exist_ok=True)
         np.savez_compressed(args.signature_out, code=out["code"], poses=out["poses"], signature=out["signature"])
         return out
+    if args.stage == "inference" and args.takes is not None:
+        src = np.load(args.code_path)
+        if 'knn_pred_takes' not in src.files:
+            raise KeyError("--takes: %s holds no knn_pred_takes (write it with GestureKNN --n_takes S)" % args.code_path)
+        index, codes = select_takes(src['knn_pred_takes'], args.takes)
+        zs = [torch.from_numpy(np.ascontiguousarray(codes.reshape(len(index), -1)))]      # (S, 30 M): ONE decode
+        poses = model.decode(zs).cpu().numpy()                                            # (S, 240 M, C)
+        save_path = os.path.join(args.save_path, args.prefix)
+        os.makedirs(save_path, exist_ok=True)
+        out_poses = np.stack([denormalize_poses(p, cfg.data_mean, cfg.data_std) for p in poses])
+        out_code = zs[0].numpy()
+        for i, k in enumerate(index):
+            tag = '%s_take%d' % (args.prefix, k)
+            np.save(os.path.join(save_path, 'code' + tag + '.npy'), out_code[i:i + 1])
+            np.save(os.path.join(save_path, 'generate' + tag + '.npy'), out_poses[i])
+            if not args.no_bvh:
+                from . import bvh
+                # (per take: the Savitzky-Golay window of --smoothing sees this take's frames only)
+                euler = bvh.poses_to_euler(poses[i], cfg.data_mean, cfg.data_std, smoothing=args.smoothing,
+                                           device="cuda:%s" % args.gpu)
+                np.save(os.path.join(save_path, tag + '_euler.npy'), euler)
+                bvh.write_bvh(os.path.join(save_path, tag + '_generated.bvh'), euler)
+        print(out_poses.shape)
+        print(out_code.shape)
+        return out_poses, out_code
     if args.stage == "inference":
         code_source = np.load(args.code_path)['knn_pred']                            # :357
         zs = [torch.from_numpy(code_source.flatten()).unsqueeze(0)]                  # :139

@@ -208,6 +208,14 @@ def _convert(args):
     return conv
 
 
+class Unsupported(RuntimeError):
+    """An entry point returned QPG_EUNSUP: the compiled kernels do not take this shape.  Nothing was launched."""
+
+
+def _raise(name, rc):
+    raise (Unsupported if rc == QPG_EUNSUP else RuntimeError)("%s failed (%d): %s" % (name, rc, last_error()))
+
+
 def call(name, device, *args):
     """Invoke a C-ABI entry point on torch's current stream of `device`; raise on error.
 
@@ -235,7 +243,7 @@ def call(name, device, *args):
         h = ctx(device)
     rc = getattr(lib, name)(h, stream, *conv)
     if rc != 0:
-        raise RuntimeError("%s failed (%d): %s" % (name, rc, last_error()))
+        _raise(name, rc)
 
 
 def prepare(name, device, *args):

@@ -453,6 +453,33 @@ def plan_step(kn, db, M, steps, mode=MODE_AUD_TXT, for_walk=False, owner_blocks=
     return StepPlan(audio, text, sharded, exchange, clip_pack, split, overlap, order)
 
 
+class TakesPlan(NamedTuple):
+    path: str           # "kernel": qpg_match_steps_takes | "per_take": one walk() per take | "unsupported"
+    reason: str         # why not "kernel" ("" when it is)
+
+
+def plan_takes(kn, db, M, steps, n_takes, serial_walk=False):
+    """How CodeKNN.walk_takes walks n_takes takes of a clip of M windows x `steps` steps: the multi-take kernels, or the
+    per-take fallback where the tabulated walk does not apply (the conditions are those of the library's
+    tabulated_walk_ok, csrc/qpg_tail.hip, which answers QPG_EUNSUP for the same cases), or not at all (row shards).
+    host_ranks tables, for_walk tables and the wavvq sweep's tables are all walked by the kernels: they only read ranks and
+    candidate indices."""
+    if db.world > 1 or kn.force_sharded:
+        return TakesPlan("unsupported", "takes of a row-sharded database are not implemented (the merged tables would serve; "
+                                        "nothing tests them)")
+    if serial_walk:
+        return TakesPlan("per_take", "the one-wave sequential walk was asked for (serial_walk)")
+    K = db.K
+    last_idx = min(steps * 4, num_frames_code) - 1
+    if (last_idx // 4 != steps - 1 or M * steps > 2048 or 2 * steps * 2 * K * 2 > 64 * 1024 or (steps * 2 * K) % 8 or
+            2 * K > 65536):
+        return TakesPlan("per_take", "the tabulated walk does not take this geometry (steps = %d, K = %d, %d steps per clip)"
+                         % (steps, K, M * steps))
+    if not 1 <= n_takes <= _lib.QPG_TAKES_MAX:
+        return TakesPlan("per_take", "n_takes outside [1, %d]" % _lib.QPG_TAKES_MAX)
+    return TakesPlan("kernel", "")
+
+
 # what CodeKNN._sweep_audio leaves: the per-shard (not yet reduced) tables, the sweep's matrix, the packed queries (the
 # sharded merge re-evaluates requested pairs from them) and the AudioPlan that was carried out
 AudioResult = namedtuple("AudioResult", "dist idx rank D q32 qn2 plan")
@@ -544,7 +571,7 @@ class CodeKNN:
         # state that appears with use: caches per shape / clip length / knobs, the side stream and its events, grown buffers
         self._qpos, self._qcache, self._layouts, self._mm_cache, self._pinned_ints, self._plans = None, {}, {}, {}, {}, {}
         self._side_stream = self._side_gate = self._side_done = self._sweep_event = None
-        self._mix_ws = self._exact_ws = self._hl_qimage = None
+        self._mix_ws = self._exact_ws = self._hl_qimage = self._takes_ws = None
         # bench.py: HIP events around the sweep kernel of every kernel_events_every-th call, appended to kernel_events
         # (a list; None: off), taken from kernel_event_pool while it lasts (events created ahead of the timed region)
         self.kernel_events, self.kernel_events_every, self.kernel_event_pool, self._ev_calls = None, 1, None, 0
@@ -1275,6 +1302,31 @@ class CodeKNN:
         self._last_gate_tables = gate                       # (tests compare the candidate tables of the two fusion paths)
         return codes_d, out_phase, votes_d
 
+    def walk_takes(self, T, n_windows, seed_codes, seed_phases, mode=MODE_AUD_TXT, window_offset=0, sync=True,
+                   seed_ptrs=None, out_pin=None, n_takes=None):
+        """Windows [window_offset, window_offset + n_windows) of the tables walked from SEVERAL seeds in one set of launches
+        (qpg_match_steps_takes; takes.py).  T: any dict sweep_tables returns on one GPU (for_walk or not,
+        host_ranks, the wavvq sweep).  seed_codes: ints [S]; seed_phases: f32 [S][8][16].
+        sync=True: (codes int64 [S, M, 30], phases f32 [S, M, steps, 8, 16], votes i32 [S, M, steps]) as NumPy arrays, every
+        take's status checked (GuardOverflow; IndexError naming the take); sync=False: the device tensors + status [S][2],
+        nothing waited for.  Take s is what walk() returns for seed s.  Which route is taken - the multi-take kernels or S
+        calls of walk() - is plan_takes' decision; a row-sharded database raises NotImplementedError.
+        seed_ptrs / out_pin / n_takes (ClipGraph): seeds read from, integer results written to pinned host memory, in
+        walk()'s several-chains layout with takes in the place of clips."""
+        from . import takes
+        return takes.walk_takes(self, T, n_windows, seed_codes, seed_phases, mode, window_offset, sync, seed_ptrs, out_pin,
+                                n_takes)
+
+    def match_clip_takes(self, test_interp, test_context, n_windows, n_takes=None, seed_codes=None, seed_phases=None,
+                         mode=MODE_AUD_TXT):
+        """One clip from several seeds: ONE sweep, one walk_takes.  Seeds not given: n_takes successive init_code_phase()
+        draws from the matcher's rng - take s is then what the s-th of n_takes successive match_clip calls on this clip
+        returns, and the rng ends in the same state.  A raised trouble word re-matches the tables once, by match_clip's
+        routes, and walks all takes from them.  Returns a takes.TakesResult: codes, phases, votes, seed_codes,
+        first_shared_code (from which code on a take repeats an earlier one) and n_distinct."""
+        from . import takes
+        return takes.match_clip_takes(self, test_interp, test_context, n_windows, n_takes, seed_codes, seed_phases, mode)
+
     @staticmethod
     def check_status(status):
         """status: the walk's two status ints on the host.  Raises what must never be ignored."""
@@ -1286,7 +1338,7 @@ class CodeKNN:
 
     def capture_clip_graph(self, n_windows, mode=MODE_AUD_TXT, n_sweep_windows=None, window_offset=0, audio=None,
                            context=None, owner_blocks=False, n_clips=1, encoder=None, encode_input=None,
-                           encode_precision="f32", sweep_signal=False, doorbell=False):
+                           encode_precision="f32", sweep_signal=False, doorbell=False, n_takes=1):
         """Capture the whole per-clip launch sequence (pack, both sweeps, per-code argmin passes, ranks,
         rank-fusion tables, walk) into one HIP graph for a fixed clip shape.  Returns a ClipGraph whose
         run(test_audio, test_context, seed_code, seed_phase) replays it; results are device tensors.
@@ -1295,10 +1347,13 @@ class CodeKNN:
         n_clips > 1 (round 5; BASELINE configs[4]): that many independent clips of n_windows windows per replay, ONE
         batched sweep and one set of walk launches for all of them (their steps back to back in the tables).
         encoder / encode_input: a VQVAE and a resident pose batch f32 [B][T][C] whose encode (make_beat_dataset.py:314-316)
-        runs INSIDE the capture on a branch of its own beside the match - one replay = the fused encode + match step."""
+        runs INSIDE the capture on a branch of its own beside the match - one replay = the fused encode + match step.
+        n_takes > 1: ONE clip per replay walked from n_takes seeds behind its one sweep (walk_takes); seeds
+        and results in the several-clips layout with takes in the place of clips (ClipGraph.run_takes / run_ints).  One GPU,
+        n_clips == 1, no encode leg, no doorbell.  With the default the capture is unchanged, node for node."""
         from .replay import ClipGraph
         return ClipGraph(self, n_windows, mode, n_sweep_windows or n_windows * n_clips, window_offset, audio, context,
-                         owner_blocks, n_clips, encoder, encode_input, encode_precision, sweep_signal, doorbell)
+                         owner_blocks, n_clips, encoder, encode_input, encode_precision, sweep_signal, doorbell, n_takes)
 
     def _tables_and_walk(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables,
                          for_walk=False):

@@ -742,6 +742,108 @@ __global__ __launch_bounds__(1024) void gate_chase_kernel(TailArgs A, const uint
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Several TAKES of one clip (qpg_match_steps_takes): the same tables walked from n_takes different seeds.  The candidate
+// tables T0 / T1 and the gate table of every step q >= 1 do not depend on the seed (the seed is read by step 0 alone),
+// so they are made once by the kernels above; what a take adds is one gate evaluation (its step 0) and one chase.
+//   step0[take]        u16: (seed code << 1) | vote of the take's first step          (takes_step0_kernel)
+//   trail[q][take]     u16: the state every take is in after step q                   (gate_chase_takes_kernel)
+// both in the caller's workspace (qpg_match_steps_takes_ws_bytes): n_takes x Q states do not fit LDS.
+// ---------------------------------------------------------------------------------------------
+#define QPG_TAKES_PER_BLOCK 64
+__host__ __device__ __forceinline__ int64_t takes_trail_off(int n_takes) { return ((int64_t)n_takes + 7) & ~(int64_t)7; }
+
+// Step 0 of every take: gate_eval with the take's own seed code and phase block, 8 lanes per take (the arithmetic of
+// gate_table_kernel's first row).  A seed code outside [0, K) is the caller's error (the host checks); it is clamped here
+// so that no table is read out of bounds.
+__global__ __launch_bounds__(256) void takes_step0_kernel(TailArgs A, int n_takes, uint16_t* __restrict__ step0) {
+  const int lane = threadIdx.x & 63;
+  const int task = (int)(((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3);
+  const bool live = task < n_takes;
+  const int take = live ? task : n_takes - 1;
+  int p = A.seed_codes[take];
+  p = p < 0 ? 0 : (p >= A.K ? A.K - 1 : p);
+  const unsigned int g = gate_eval(A, 0, p, A.seed_phase + (int64_t)take * 128, lane);
+  if (live && (lane & 7) == 0) step0[take] = (uint16_t)g;
+}
+
+// The chase of up to 64 takes per block, one lane of wave 0 per take: a window's gate table is staged into LDS ONCE for
+// all takes of the block (double-buffered: the other waves stage window w + 1 while wave 0 chases window w), and every
+// take follows its own state through it.  The trail's stores are coalesced over the takes and off the dependent chain.
+__global__ __launch_bounds__(1024) void gate_chase_takes_kernel(int M, int steps, int K, int n_takes,
+                                                                const uint16_t* __restrict__ Gt,
+                                                                const uint16_t* __restrict__ step0,
+                                                                uint16_t* __restrict__ trail) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t gl[];     // 2 x [steps][2K]
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int per_w = steps * 2 * K;                                  // u16 per window
+  const int take = blockIdx.x * QPG_TAKES_PER_BLOCK + tid;
+  const bool chaser = tid < QPG_TAKES_PER_BLOCK && take < n_takes;
+  auto stage = [&](int w, int first, int step) {
+    const int4* src = reinterpret_cast<const int4*>(Gt + (int64_t)w * per_w);
+    int4* dst = reinterpret_cast<int4*>(gl + (size_t)(w & 1) * per_w);
+    for (int v = first; v < per_w / 8; v += step) dst[v] = src[v];
+  };
+  stage(0, tid, nt);
+  __syncthreads();
+  int sigma = chaser ? step0[take] : 0;
+  for (int w = 0; w < M; ++w) {
+    if (tid >= 64 && w + 1 < M) stage(w + 1, tid - 64, nt - 64);
+    if (chaser) {
+      const uint16_t* g = gl + (size_t)(w & 1) * per_w;
+      for (int s = 0; s < steps; ++s) {
+        if (w | s) sigma = g[s * 2 * K + sigma];                    // (a table entry is (p << 1) | vote < 2K)
+        trail[(int64_t)(w * steps + s) * n_takes + take] = (uint16_t)sigma;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// gate_chase_kernel's parallel epilogue, one block per take: the winners' phase blocks, votes, codes, the absent-candidate
+// check of every visited gate, and the take's status pair last, behind the system-scope fence.
+__global__ __launch_bounds__(256) void takes_epilogue_kernel(TailArgs A, int n_takes, const uint16_t* __restrict__ trail) {
+  __shared__ uint16_t sig[QPG_CHASE_QMAX];
+  __shared__ int bad_s;
+  const int K = A.K, Q = A.M * A.steps, tid = threadIdx.x, nt = blockDim.x;
+  const int take = blockIdx.x;
+  A.out_phase += (int64_t)take * Q * 128;
+  A.out_vote += (int64_t)take * Q;
+  A.out_codes += (int64_t)take * A.M * A.codes_per_window;
+  A.out_status += (int64_t)take * A.status_stride;
+  if (tid == 0) bad_s = 0;
+  for (int q = tid; q < Q; q += nt) sig[q] = trail[(int64_t)q * n_takes + take];
+  __syncthreads();
+  for (int i = tid; i < Q * 32; i += nt) {                         // 32 x 16 B per phase block
+    const int q = i >> 5, v = i & 31;
+    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
+    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
+    int pb;
+    const float* blk = cand_block(A, fi, ci, &pb) + 384;
+    reinterpret_cast<f32x4*>(A.out_phase + (int64_t)q * 128)[v] = reinterpret_cast<const f32x4*>(blk)[v];
+    if (v == 0) {
+      A.out_vote[q] = fi;
+      if (A.T0[(int64_t)q * K + p] < 0 || A.T1[(int64_t)q * K + p] < 0) bad_s = 1;
+    }
+  }
+  for (int i = tid; i < A.M * A.codes_per_window; i += nt) {
+    const int w = i / A.codes_per_window, c = i - w * A.codes_per_window;
+    const int q = w * A.steps + c / A.step_codes;
+    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
+    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
+    int pb;
+    cand_block(A, fi, ci, &pb);
+    A.out_codes[i] = A.code[pb + c % A.step_codes];
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (tid == 0) {
+    A.out_status[0] = bad_s;
+    __threadfence_system();
+    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
+  }
+}
+
 __global__ void status_only_kernel(int32_t* out_status, const int32_t* guard_flags) {
   out_status[0] = 0;
   out_status[1] = guard_flags ? guard_flags[0] : 0;
@@ -764,6 +866,16 @@ extern "C" int qpg_fuse_best_ranked(qpg_ctx* ctx, void* stream, const int16_t* r
 // From how many chains per launch the gate table is deduplicated by the previous winner (gate_table_dedup_kernel; 0 =
 // never): the context's QPG_OPT_GATE_DEDUP_FROM_CHAINS (default 1; the tests set 0 to walk on round 4's plain table).
 
+// The tabulated walk applies when the code that seeds the next window comes from the window's LAST step (always true for
+// the reference's grids: 8 steps x 4 codes, 30 kept) and the state fits 16 bits; the one-wave sequential walk otherwise.
+static bool tabulated_walk_ok(bool serial_walk, int steps, int K, int Qc, GateGeom* geo) {
+  const int codes_per_window = (steps * 4 < 30) ? steps * 4 : 30, last_idx = codes_per_window - 1;
+  *geo = GateGeom{last_idx / 4, last_idx % 4};
+  const size_t lds_g = (size_t)2 * steps * 2 * K * sizeof(uint16_t);     // two window tables (double buffer)
+  return !serial_walk && geo->s_last == steps - 1 && 2 * K <= 65536 && Qc <= QPG_CHASE_QMAX && lds_g <= 64 * 1024 &&
+         ((steps * 2 * K) % 8) == 0;
+}
+
 static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
                             const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
                             const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx,
@@ -771,7 +883,8 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
                             int Gt, const float* phase, int Tp, int mode, int M, int steps, int K, int seed_code,
                             const float* seed_phase, int32_t* gate_tables, int32_t* out_codes, float* out_phase,
                             int32_t* out_vote, int32_t* out_status, const int32_t* guard_flags, int n_chains,
-                            const int32_t* seed_codes, int64_t status_stride) {
+                            const int32_t* seed_codes, int64_t status_stride, int n_takes = 0,
+                            void* takes_ws = nullptr, size_t takes_ws_bytes = 0) {
   QPG_REQUIRE(ctx && pos_rank && freq_rank && code && phase && seed_phase && gate_tables && out_codes && out_phase &&
                   out_vote && out_status,
               "qpg_match_steps: null pointer");
@@ -798,6 +911,15 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
   }
   const int Qc = M * steps;                  // steps of one chain
   const int Q = Qc * n_chains;
+  GateGeom geo;
+  const bool tabulated = tabulated_walk_ok(serial_walk, steps, K, Qc, &geo);
+  if (n_takes > 0 && !tabulated) {           // (before anything is launched: the caller walks the takes one by one)
+    qpg_set_error("qpg_match_steps_takes: the tabulated walk does not apply (serial walk asked for, or steps = %d / K = %d "
+                  "/ %d steps per clip outside its geometry)", steps, K, Qc);
+    return QPG_EUNSUP;
+  }
+  QPG_REQUIRE(n_takes <= 0 || (takes_ws && takes_ws_bytes >= qpg_match_steps_takes_ws_bytes(n_takes, M, steps)),
+              "qpg_match_steps_takes: workspace too small (qpg_match_steps_takes_ws_bytes)");
   int32_t* T0 = gate_tables;
   int32_t* T1 = gate_tables + (int64_t)Q * K;
   if (prefused) {
@@ -822,13 +944,7 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
   A.status_stride = status_stride;
   A.out_codes = out_codes; A.out_phase = out_phase; A.out_vote = out_vote; A.out_status = out_status;
   A.guard_flags = guard_flags;
-  // tabulated walk when the code that seeds the next window comes from the window's LAST step (always true for the
-  // reference's grids: 8 steps x 4 codes, 30 kept) and the state fits 16 bits; the one-wave sequential walk otherwise
-  const int last_idx = A.codes_per_window - 1;
-  GateGeom geo{last_idx / A.step_codes, last_idx % A.step_codes};
   const size_t lds_g = (size_t)2 * steps * 2 * K * sizeof(uint16_t);     // two window tables (double buffer)
-  const bool tabulated = !serial_walk && geo.s_last == steps - 1 && 2 * K <= 65536 && Qc <= QPG_CHASE_QMAX &&
-                         lds_g <= 64 * 1024 && ((steps * 2 * K) % 8) == 0;
   if (!tabulated) {
     QPG_REQUIRE(n_chains == 1, "qpg_match_steps_batch: the sequential walk takes one chain per call");
     hipLaunchKernelGGL(match_walk_kernel, dim3(1), dim3(64), lds, qpg_stream(stream), A);
@@ -845,6 +961,29 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
     hipLaunchKernelGGL(gate_table_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, qpg_stream(stream), A,
                        geo, gtab);
     QPG_LAUNCH_CHECK("gate_table_kernel");
+  }
+  if (n_takes > 0) {
+    // the gate table above is the clip's (its row 0 holds take 0's step); every take's step 0, chase and epilogue
+    uint16_t* step0 = reinterpret_cast<uint16_t*>(takes_ws);
+    uint16_t* trail = step0 + takes_trail_off(n_takes);
+    const int stages = ctx->opt[QPG_OPT_TAKES_STAGES];                  // (7 unless a measurement asked for less)
+    if (stages & 1) {
+      hipLaunchKernelGGL(takes_step0_kernel, dim3((unsigned)(((int64_t)n_takes * 8 + 255) / 256)), dim3(256), 0,
+                         qpg_stream(stream), A, n_takes, step0);
+      QPG_LAUNCH_CHECK("takes_step0_kernel");
+    }
+    if (stages & 2) {
+      hipLaunchKernelGGL(gate_chase_takes_kernel,
+                         dim3((unsigned)((n_takes + QPG_TAKES_PER_BLOCK - 1) / QPG_TAKES_PER_BLOCK)), dim3(1024), lds_g,
+                         qpg_stream(stream), M, steps, K, n_takes, (const uint16_t*)gtab, (const uint16_t*)step0, trail);
+      QPG_LAUNCH_CHECK("gate_chase_takes_kernel");
+    }
+    if (stages & 4) {
+      hipLaunchKernelGGL(takes_epilogue_kernel, dim3((unsigned)n_takes), dim3(256), 0, qpg_stream(stream), A, n_takes,
+                         (const uint16_t*)trail);
+      QPG_LAUNCH_CHECK("takes_epilogue_kernel");
+    }
+    return QPG_OK;
   }
   hipLaunchKernelGGL(gate_chase_kernel, dim3(n_chains), dim3(1024), lds_g, qpg_stream(stream), A, (const uint16_t*)gtab);
   QPG_LAUNCH_CHECK("gate_chase_kernel");
@@ -879,4 +1018,30 @@ extern "C" int qpg_match_steps_batch(qpg_ctx* ctx, void* stream, const int16_t* 
   return match_steps_impl(ctx, stream, aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx,
                           aud_pslot, Ga, txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, 0, seed_phase, gate_tables,
                           out_codes, out_phase, out_vote, out_status, guard_flags, n_chains, seed_codes, status_stride);
+}
+
+// n_takes takes of ONE clip (tables of Q = M x steps rows) in one set of launches: rank fusion (unless prefused) and the
+// gate table once, by the kernels qpg_match_steps runs - the same bits -, then step 0 of every take, the takes' chases
+// (64 takes per block, a window's table staged once per block) and one epilogue block per take.  include/qpg.h has the
+// arguments.  QPG_EUNSUP where the tabulated walk does not apply: nothing has been launched then.
+extern "C" size_t qpg_match_steps_takes_ws_bytes(int n_takes, int M, int steps) {
+  if (n_takes < 1 || M < 1 || steps < 1) return 0;
+  return sizeof(uint16_t) * (size_t)(takes_trail_off(n_takes) + (int64_t)M * steps * n_takes);
+}
+
+extern "C" int qpg_match_steps_takes(qpg_ctx* ctx, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
+                                     const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
+                                     const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx,
+                                     const int32_t* aud_pslot, int Ga, const int32_t* txt_cidx, const int32_t* txt_pslot,
+                                     int Gt, const float* phase, int Tp, int mode, int M, int steps, int K,
+                                     int n_takes, const int32_t* seed_codes, const float* seed_phase,
+                                     int32_t* gate_tables, int32_t* out_codes, float* out_phase, int32_t* out_vote,
+                                     int32_t* out_status, int64_t status_stride, const int32_t* guard_flags,
+                                     void* workspace, size_t workspace_bytes) {
+  QPG_REQUIRE(M > 0 && seed_codes && n_takes >= 1 && n_takes <= QPG_TAKES_MAX && status_stride >= 2,
+              "qpg_match_steps_takes: M > 0, 1 <= n_takes <= %d, device seed codes and a status stride >= 2", QPG_TAKES_MAX);
+  return match_steps_impl(ctx, stream, aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx,
+                          aud_pslot, Ga, txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, 0, seed_phase, gate_tables,
+                          out_codes, out_phase, out_vote, out_status, guard_flags, 1, seed_codes, status_stride, n_takes,
+                          workspace, workspace_bytes);
 }

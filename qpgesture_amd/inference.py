@@ -36,12 +36,20 @@ def knn_command(test_data, out_knn_filename, train_database, train_codebook, cod
     return cmd + list(extra)
 
 
+def takes_flags(n_takes=1, takes=None):
+    """The extra flags of the two command lines for several takes: nothing for the defaults."""
+    return (['--n_takes', str(int(n_takes))] if int(n_takes) != 1 else []) + \
+        (['--takes', str(takes)] if takes is not None else [])
+
+
 def main(test_data, config, VQVAE_model_path, output_fold=None, prefix=None, gpu='0', subprocess=False, no_bvh=False,
-         knn_extra=(), **db_paths):
+         knn_extra=(), n_takes=1, takes=None, **db_paths):
     """test_data: the utterance's `<name>_norm_mfcc.npz` (inference.py:51-54 writes it).  db_paths: train_database,
     train_codebook, codebook_signature, train_wavlm, test_wavlm (, train_wavvq, test_wavvq) - inference.py:57-65.
     Writes `<output_fold>/knn_pred.npz` and `<output_fold>/result_<name>/generateresult_<name>.npy` (+ the BVH unless
-    no_bvh), the reference's file names (:21-23, :68).  Returns (knn_pred int64 (M,30), poses f32 (240 M, 135))."""
+    no_bvh), the reference's file names (:21-23, :68).  Returns (knn_pred int64 (M,30), poses f32 (240 M, 135)).
+    n_takes / takes: GestureKNN's --n_takes and VisualizeCodebook's --takes, passed through (several matched clips from one
+    sweep, decoded in one batch; with `takes` the poses returned are the selected takes' (S, 240 M, 135))."""
     import numpy as np
     name = os.path.basename(test_data)
     for suffix in ('_norm_mfcc.npz', '_mfcc.npz', '.npz'):
@@ -51,7 +59,7 @@ def main(test_data, config, VQVAE_model_path, output_fold=None, prefix=None, gpu
     output_fold = output_fold or os.path.dirname(os.path.abspath(test_data))
     os.makedirs(output_fold, exist_ok=True)
     out_knn = os.path.join(output_fold, 'knn_pred.npz')
-    argv = knn_command(test_data, out_knn, extra=knn_extra, **db_paths)
+    argv = knn_command(test_data, out_knn, extra=list(knn_extra) + takes_flags(n_takes, None), **db_paths)
     if subprocess:                                               # inference.py:66 subprocess.call(cmd)
         rc = _subprocess.call([sys.executable, '-m', 'qpgesture_amd.GestureKNN'] + argv)
         if rc != 0:
@@ -62,12 +70,13 @@ def main(test_data, config, VQVAE_model_path, output_fold=None, prefix=None, gpu
     from . import VisualizeCodebook
     prefix = prefix or ('result_' + name)                        # inference.py:68
     vis = ['--config', config, '--gpu', str(gpu), '--code_path', out_knn, '--VQVAE_model_path', VQVAE_model_path,
-           '--stage', 'inference', '--prefix', prefix, '--save_path', output_fold] + (['--no_bvh'] if no_bvh else [])
+           '--stage', 'inference', '--prefix', prefix, '--save_path', output_fold] + (['--no_bvh'] if no_bvh else []) + \
+        takes_flags(1, takes)
     poses, _ = VisualizeCodebook.main(vis)
     return np.load(out_knn)['knn_pred'], poses
 
 
-def _cli(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for k in ('test_data', 'train_database', 'train_codebook', 'codebook_signature', 'train_wavlm', 'test_wavlm', 'config',
               'VQVAE_model_path'):
@@ -79,7 +88,13 @@ def _cli(argv=None):
     p.add_argument('--gpu', default='0')
     p.add_argument('--subprocess', action='store_true', help='run GestureKNN as a child process, as the reference does')
     p.add_argument('--no_bvh', action='store_true')
-    a = p.parse_args(argv)
+    p.add_argument('--n_takes', type=int, default=1, help='GestureKNN --n_takes: matched clips per utterance')
+    p.add_argument('--takes', default=None, help="VisualizeCodebook --takes: 'all' or a take's index")
+    return p
+
+
+def _cli(argv=None):
+    a = build_parser().parse_args(argv)
     kw = {k: v for k, v in vars(a).items() if v is not None}
     return main(**kw)
 

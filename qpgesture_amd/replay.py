@@ -27,9 +27,21 @@ class ClipGraph:
     sentinel, hipGraphLaunch, watch the status word.  One capture serves every clip of that shape."""
 
     def __init__(self, knn, n_windows, mode, n_sweep_windows, window_offset, audio=None, context=None, owner_blocks=False,
-                 n_clips=1, encoder=None, encode_input=None, encode_precision="f32", sweep_signal=False, doorbell=False):
+                 n_clips=1, encoder=None, encode_input=None, encode_precision="f32", sweep_signal=False, doorbell=False,
+                 n_takes=1):
         db, dev = knn.db, knn.db.device
         self.owner_blocks = owner_blocks
+        # n_takes > 1 (DESIGN.md 4.7): ONE clip per replay, walked from n_takes seeds behind its one sweep
+        # (CodeKNN.walk_takes).  The seed block and the pinned results keep the several-clips layout with takes in the place
+        # of clips, so launch / wait_ints / run_ints / codes() / statuses() work as they are.
+        self.n_takes = int(n_takes)
+        if self.n_takes < 1:
+            raise ValueError("n_takes >= 1")
+        if self.n_takes > 1:
+            if db.world != 1 or knn.force_sharded:
+                raise NotImplementedError("several takes per replay: one GPU only (no row-sharded database)")
+            if int(n_clips) != 1 or encoder is not None or encode_input is not None or doorbell:
+                raise NotImplementedError("several takes per replay: n_clips == 1, no encode leg, no doorbell")
         # doorbell (round 6): the capture's FIRST node waits for the host's go (qpg_doorbell_wait), so the NEXT replay can be
         # enqueued while the current one still runs (prelaunch(): hipGraphLaunch is ~17 us of host time + the command
         # processor's start-up) and started by ONE store once the current results are read and the next seed is written
@@ -49,6 +61,8 @@ class ClipGraph:
         self.CL = int(n_clips)
         if self.CL < 1 or n_sweep_windows < window_offset + self.CL * n_windows:
             raise ValueError("n_clips x n_windows windows must lie inside the swept windows")
+        if self.n_takes > 1:
+            self.CL = self.n_takes          # (the layouts below: one seed, one result row, one status pair per take)
         self.enc, self.enc_x = encoder, encode_input
         if (encoder is None) != (encode_input is None):
             raise ValueError("encoder and encode_input go together")
@@ -189,6 +203,13 @@ class ClipGraph:
                                  for_walk=True, after_sweep=behind_sweep)
             if self.enc is not None:
                 main.wait_event(self._enc_done)
+            if self.n_takes > 1:
+                out = knn.walk_takes(T, self.M, None, None, mode=self.mode, window_offset=self._off, sync=False,
+                                     seed_ptrs=ptrs, out_pin=self._pin, n_takes=self.n_takes)
+                # (the capture holds the address of the takes' workspace: an eager call with more takes makes the matcher
+                # grow a new one, and this one must stay allocated for as long as the graph can be replayed)
+                self._takes_ws = knn._takes_ws
+                return out
             return knn.walk(T, self.M, self._off, self.mode, sync=False, seed_ptrs=ptrs, out_pin=self._pin,
                             n_chains=self.CL)
         import os as _os
@@ -370,6 +391,26 @@ class ClipGraph:
         """One replay on the bound inputs, ending with the integer results on the host (bench.py's graph step)."""
         self.launch(seed_code, seed_phase)
         return self.wait_ints()
+
+    def run_takes(self, seed_codes, seed_phases):
+        """n_takes graphs: one replay on the bound / static inputs from these seeds (ints [n_takes], f32 [n_takes][8][16])
+        -> a takes.TakesResult, as CodeKNN.match_clip_takes returns it.  A replay whose trouble word is raised goes through
+        match_clip_takes (which re-matches the tables on a path that cannot raise it) with the same seeds."""
+        from . import takes
+        S, M = self.CL, self.M
+        sc, sp = takes.check_seeds(seed_codes, seed_phases, self.knn.db.K)
+        if self.n_takes < 2 or sc.size != S:
+            raise ValueError("run_takes: a graph captured with n_takes = %d wants that many seeds" % self.n_takes)
+        ints = self.run_ints(sc, sp)
+        try:
+            takes.check_statuses(self.statuses(ints))
+        except GuardOverflow:
+            o = self._off
+            return self.knn.match_clip_takes(self.audio[o:o + M].contiguous(), self.context[o:o + M].contiguous(), M,
+                                             seed_codes=sc, seed_phases=sp, mode=self.mode)
+        codes = self.codes(ints).astype(np.int64)
+        votes = ints[S * self._n_c:S * (self._n_c + self._n_v)].reshape(S, M, -1).copy()
+        return takes.make_result(codes, self.out[1].cpu().numpy(), votes, sc)
 
     def run(self, test_audio, test_context, seed_code, seed_phase):
         """Copies the clip into the static buffers (skipped for the tensors the graph is bound to) and replays.  Returns
