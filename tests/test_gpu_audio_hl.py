@@ -1,7 +1,8 @@
 """Split-operand f16 audio sweep (qpg_audio_cosine_hl, csrc/qpg_audio_hl.hip): (1) the one measured constant of its
 a-priori bound - how far a v_mfma_f32_16x16x32_f16 block sum is from the exact sum of its 32 products; (2) the bound
 itself, measured against the f64 sweep on awkward data; (3) CodeKNN on this kernel returns the reference's tables and
-codes (goldens) and the same winners / ranks as on the f32-matrix-core kernel."""
+codes (goldens) and the same winners / ranks as on the f32-matrix-core kernel; (4) the same bound for the one-plane sweep
+of an f16-stored track (qpg_audio_cosine_hl1), at the kernel's own level."""
 import numpy as np
 import pytest
 
@@ -190,6 +191,82 @@ def test_hl_sweep_flags_operands_outside_its_range(quiet):
     ok = np.ones(D64.shape[1], bool)
     ok[20 * 26:21 * 26] = False
     assert np.abs(D64 - Dhl)[:, ok].max() <= AUDIO_MX_ERR
+
+
+def _sweeps_hl1(N, Q, seed, F=1024, quiet=None):
+    """The one-plane sweep (qpg_audio_hl1_pack_db + qpg_audio_cosine_hl1: the track stored in f16, BASELINE configs[4])
+    against qpg_audio_cosine_f64 on the WIDENED ROUNDED track, into matrices pre-filled with NaN.  -> D64, D (f64 matrix),
+    D32 (f32 matrix, widened), stats."""
+    import torch
+    from qpgesture_amd import _lib
+    dev = torch.device("cuda:0")
+    T, G = 180, 26
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    base = torch.randn((N, T, F), generator=g)
+    if N > 12:
+        base[3] = 0.0                                              # an all-zero window
+        base[5, 100:] = 0.0
+        base[7] *= 0.05                                            # a quiet window and a loud stretch (f16: up to ~150)
+        base[9, 40:90] *= 30.0
+        if quiet is not None:
+            base[10] *= quiet
+    base_h = base.to(torch.float16).to(dev).contiguous()
+    base = base_h.float()                                          # everything is defined on the rounded track
+    q32 = torch.randn((Q, 6 * F), generator=g).to(dev)
+    if Q > 11:
+        q32[7] = 0.0
+        q32[9] = base[min(11, N - 1), 12:24:2].reshape(-1)         # a query that IS a candidate (distance ~ 0)
+        q32[10] *= 1e-3
+        q32[11] *= 1e3
+    cand_t = (torch.arange(G, dtype=torch.int32) * 6).to(dev)
+    fn2 = torch.empty((N, T), dtype=torch.float64, device=dev)
+    _lib.call("qpg_frame_norm2_f64", dev, base, N * T, F, fn2)
+    cn2 = torch.empty((N, G), dtype=torch.float64, device=dev)
+    _lib.call("qpg_audio_cand_norm2", dev, fn2, N, T, cand_t, G, 6, 2, cn2)
+    qn2 = (q32.double() ** 2).sum(1)
+    D64 = torch.empty((Q, N * G), dtype=torch.float64, device=dev)
+    _lib.call("qpg_audio_cosine_f64", dev, base, N, T, F, cand_t, G, 6, 2, cn2, q32, qn2, Q, D64, D64.stride(0))
+    lib = _lib.load()
+    assert lib.qpg_audio_hl1_supported(T, F, G, 6, 2, 6)
+    img = torch.empty((int(lib.qpg_audio_hl1_db_bytes(N, F)),), dtype=torch.uint8, device=dev)
+    _lib.call("qpg_audio_hl1_pack_db", dev, base_h, N, T, F, G, 6, 2, 6, img, img.numel())
+    qi = torch.empty((int(lib.qpg_audio_hl_query_bytes(Q, F)),), dtype=torch.uint8, device=dev)
+    _lib.call("qpg_audio_hl_pack_queries", dev, q32, Q, F, qi, qi.numel())
+    stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+    Dh = torch.full((Q, N * G), float("nan"), dtype=torch.float64, device=dev)
+    _lib.call("qpg_audio_cosine_hl1", dev, img, N, F, G, cn2, qi, qn2, Q, Dh, 0, Dh.stride(0), stats)
+    D32 = torch.full((Q, N * G), float("nan"), dtype=torch.float32, device=dev)
+    _lib.call("qpg_audio_cosine_hl1", dev, img, N, F, G, cn2, qi, qn2, Q, D32, 1, D32.stride(0), stats)
+    torch.cuda.synchronize()
+    return D64.cpu().numpy(), Dh.cpu().numpy(), D32.double().cpu().numpy(), stats.cpu().numpy()
+
+
+@pytest.mark.parametrize("Q,N,F", [(48, 96, 1024), (16, 37, 1024), (5, 8, 1024), (100, 50, 1024), (768, 24, 1024),
+                                   (48, 700, 1024), (48, 33, 256), (100, 50, 256), (16, 37, 128), (100, 50, 128)])
+def test_hl1_sweep_stays_inside_the_error_bound(Q, N, F):
+    """The one-plane sweep's a-priori bound at the kernel's own level (until now only through the matcher at N = 2048,
+    Q = 48, F = 1024: one chunk of queries, the non-temporal-load instantiation, no ragged N): the (Q, N) list of the
+    two-plane test - one and several query chunks, ragged window groups - and F = 256 / 128 (3 F / 32 = 24 and 12: two trips
+    and ONE trip of the k loop), both matrix types, every entry written, zero rows and zero queries exact.
+    The out-of-range guard: the one-plane kernel has NO database-side guard - its image holds the f16 database exactly, so
+    there is no representation error a quiet window could fall out of (csrc/qpg_audio_hl.hip: the stats[1] |= 2 test is
+    compiled for the two-plane image only); the query-side half of the guard is the two-plane kernel's own code.  A window
+    3e-4 as loud as the rest (its values reach f16's subnormals; the case that flags the two-plane sweep) therefore has to
+    stay inside the bound without a flag: the N = 96 case plants one."""
+    from qpgesture_amd.code_knn import AUDIO_HL_ERR
+    D64, Dh, D32, stats = _sweeps_hl1(N, Q, seed=Q + N + F, F=F, quiet=3e-4 if N == 96 else None)
+    assert not np.isnan(Dh).any() and not np.isnan(D32).any()      # every (query, candidate) was written
+    assert np.array_equal(D32, Dh.astype(np.float32).astype(np.float64))
+    e64, e32 = np.abs(D64 - Dh), np.abs(D64 - D32)
+    print("hl1 N=%d Q=%d F=%d: max |D_hl1 - D_f64| = %.3g (f64 matrix), %.3g (f32 matrix); bound %.3g; mean %.3g"
+          % (N, Q, F, e64.max(), e32.max(), AUDIO_HL_ERR, e64.mean()))
+    assert e64.max() <= AUDIO_HL_ERR and e32.max() <= AUDIO_HL_ERR
+    assert stats[1] == 0
+    if N > 12:
+        assert np.array_equal(D64[:, 3 * 26:4 * 26], Dh[:, 3 * 26:4 * 26])   # zero candidate rows: exact in both
+        assert np.array_equal(D64[:, 3 * 26:4 * 26], D32[:, 3 * 26:4 * 26])
+    if Q > 11:
+        assert np.array_equal(D64[7], Dh[7]) and np.array_equal(D64[7], D32[7])   # zero query row: exact
 
 
 def _build(A, freq_rank, kernel, dev="cuda:0"):

@@ -4,7 +4,7 @@ on one GPU): (1) the sweep's a-priori error bound holds, measured; (2) winners, 
 import numpy as np
 import pytest
 
-from tests.helpers import fixture_arrays, load_golden
+from tests.helpers import fixture_arrays, load_golden, merge_mixed_by_hand
 
 pytestmark = pytest.mark.gpu
 
@@ -160,8 +160,7 @@ def test_sharded_mixed_merge_protocol_on_one_gpu():
     (perturbed copies of shard-0 windows live in shard 1, half of them with the same codes).  Winners and ranks must equal
     the unsharded f64 tables."""
     import torch
-    from qpgesture_amd import _lib
-    from qpgesture_amd.code_knn import ABSENT_DIST, AUDIO_MX_BAND, CodeKNN, ExchangeLayout, GestureDB
+    from qpgesture_amd.code_knn import AUDIO_MX_BAND, CodeKNN, ExchangeLayout, GestureDB
     ntr, nte, W = 120, 2, 2
     A = fixture_arrays(ntr, nte, 70, 71, 72, 73)
     rng = np.random.Generator(np.random.PCG64(9))
@@ -196,33 +195,11 @@ def test_sharded_mixed_merge_protocol_on_one_gpu():
     recv = torch.cat([l.send for l in lays])                 # what the all-gather leaves on every rank
     src_stride = lays[0].send.numel()
     R = 4096
-    req_stride, resp_stride = 8 + 8 * R, 8 + 8 * R
-    owner = shards[0]
-    req = torch.zeros((W * req_stride,), dtype=torch.uint8, device=dev)
-    ws = torch.empty((int(_lib.load().qpg_merge_mixed_ws_bytes(Q, K, 1024)),), dtype=torch.uint8, device=dev)
-    stats = torch.zeros((4,), dtype=torch.int32, device=dev)
-    _lib.call("qpg_merge_mixed_phase1_f64", dev, recv, W, src_stride, lays[0].off["aud_d"], lays[0].off["aud_i"], Q, K,
-              float(ABSENT_DIST), AUDIO_MX_BAND, R, req, req_stride, ws, ws.numel(), stats, 1024, -1)
-    counts = [int(req[w * req_stride:w * req_stride + 4].view(torch.int32)[0]) for w in range(W)]   # header: count | flags
+    refine = [dict(cand_base=k.db.idx_base * k.db.Ga, base=k.db.base, base_is_f16=0, T=k.db.T, F=k.db.F, cand_t=k.db.aud_t,
+                   G=k.db.Ga, tap_stride=k.db.tap_stride, q32=k._last_q32, qn2=k._last_qn2, cn2=k.db.cn2) for k in shards]
+    d, ix, rk, st, counts = merge_mixed_by_hand(recv, W, src_stride, lays[0].off["aud_d"], lays[0].off["aud_i"], Q, K,
+                                                AUDIO_MX_BAND, 1e-12, refine, R=R, fl_cap=1024)
     assert min(counts) > 0 and max(counts) <= R              # both shards are asked (the near-ties straddle the boundary)
-    resp_recv = torch.zeros((W * resp_stride,), dtype=torch.uint8, device=dev)
-    for w in range(W):                                       # all-to-all by hand: owner 0's block w -> shard w's block 0
-        req_recv = torch.full((W * req_stride,), 255, dtype=torch.uint8, device=dev)      # (unused slots / blocks: ~0)
-        for b in range(W):
-            req_recv[b * req_stride:b * req_stride + 8] = 0                       # headers: count | flags
-        req_recv[:req_stride] = req[w * req_stride:(w + 1) * req_stride]
-        resp = torch.zeros((W * resp_stride,), dtype=torch.uint8, device=dev)
-        k, db = shards[w], shards[w].db
-        _lib.call("qpg_shard_refine_f64", dev, req_recv, W, req_stride, R, 0, db.idx_base * db.Ga, db.base, 0, db.T, db.F,
-                  db.aud_t, db.Ga, 6, db.tap_stride, k._last_q32, k._last_qn2, db.cn2, resp, resp_stride, 0, None, R // Q)
-        resp_recv[w * resp_stride:(w + 1) * resp_stride] = resp[:resp_stride]
-    d = torch.empty((Q, K), dtype=torch.float64, device=dev)
-    ix = torch.empty((Q, K), dtype=torch.int32, device=dev)
-    rk = torch.empty((Q, K), dtype=torch.int16, device=dev)
-    _lib.call("qpg_merge_mixed_phase2_f64", dev, recv, W, src_stride, lays[0].off["aud_i"], Q, K, float(ABSENT_DIST), ws,
-              ws.numel(), resp_recv, resp_stride, d, ix, rk, stats, 1024, 1e-12)
-    torch.cuda.synchronize()
-    st = stats.cpu().numpy()
     print("requests per shard", counts, " cross-shard re-evaluations", int(st[3]), " flags", int(st[1]))
     # (flag 8 = FLAG_CROSS_SHARD_TIE: the planted EXACT duplicates across the shard boundary tie below 1e-12, which the
     # dot-product responses cannot order like the reference for sure - the host would re-match this clip on the exact
