@@ -1,7 +1,7 @@
-"""Where does the conv kernel's time go?  Builds libqpg_hip.so variants with parts of the K loop compiled out
-(-DQPG_CONV_PROBE=1: no global fetch; =2: no fetch, no LDS commit, no barriers) and times the B=256 encode.
-Results are numerically meaningless for the probe builds; only the time matters."""
-import os, subprocess, sys, time
+"""Where does the conv kernel's time go?  Times the B=256 encode (variant "0") or the f64 audio sweep (variant "a0") of
+the product library, or the encode of a library given by path.  (The variants with parts of the K loop compiled out
+needed the -DQPG_CONV_PROBE / -DQPG_AUDIO_PROBE hooks: see README.md.)"""
+import os, sys, time
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
@@ -9,20 +9,8 @@ variant = sys.argv[1]
 import qpgesture_amd._lib as L
 if variant.endswith(".so"):
     L.LIB_PATH = os.path.abspath(variant)
-elif variant not in ("0", "a0"):
-    so = os.path.join(HERE, "libqpg_probe%s.so" % variant)
-    csrc = os.path.join(ROOT, "qpgesture_amd", "csrc")
-    srcs = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip"))
-    if not os.path.exists(so):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                               "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
-                               "-DQPG_AUDIO_PROBE=1" if variant == "a" else "-DQPG_CONV_PROBE=" + variant]
-                              + srcs + ["-o", so])
-    L.LIB_PATH = so
 import torch
-if variant in ("a", "a0"):
-    if variant == "a0":
-        pass
+if variant == "a0":
     N, Q, T, F, G = 2048, 48, 180, 1024, 26
     dev = torch.device("cuda:0")
     base = torch.randn((N, T, F), device=dev)

@@ -915,14 +915,13 @@ int qpg_conv1d_bwd_weight_f32(qpg_ctx*, void* stream, const float* x, int B, int
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load
- * through QPG_LIB_PATH); in libqpg_hip.so every one of these knobs is a compile-time constant and the symbols do not
- * exist (tests/test_host_cpu.py asserts that).  Process-wide where they exist.
+ * through QPG_LIB_PATH); in libqpg_hip.so what each of the three sets is a compile-time constant and the symbols
+ * do not exist (tests/test_host_cpu.py asserts that).  Process-wide where they exist.
  * ---------------------------------------------------------------------------------------- */
 #ifdef QPG_DEBUG_HOOKS
 int qpg_debug_gemm64_waves(int nw);                  /* waves per block of qpg_hl_gemm_tilemin_h's kernel: 4 (default) or 8 */
 int qpg_debug_convt_shape(int nq, int pd);           /* force the short-sequence convolution kernel's block shape */
 int qpg_debug_convt_opts(int deep_ring, int xcd_map);/* deep fragment ring / XCD map of that kernel (measured, off) */
-int qpg_debug_select_prof(long long* out);           /* -DQPG_SELECT_PROF section timers of the mixed select */
 #endif
 
 #ifdef __cplusplus

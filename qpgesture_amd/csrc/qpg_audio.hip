@@ -138,11 +138,6 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
     f32x4 a[MT][2], b[NT][2];
   };
   auto load = [&](Buf& u, int e0, int tap) {
-#if defined(QPG_AUDIO_PROBE)     // experiments/conv_probe: operands from constants, no loads
-    for (int mt = 0; mt < MT; ++mt) u.a[mt][0] = u.a[mt][1] = (f32x4){1.f, 1.f, 1.f, 1.f};
-    for (int nt = 0; nt < NT; ++nt) u.b[nt][0] = u.b[nt][1] = (f32x4){1.f, 1.f, 1.f, 1.f};
-    return;
-#endif
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       // taps past the end of the window are zero padding (data_processing.py:266): the load is unconditional (a
@@ -197,9 +192,7 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
   // spread between the MFMAs — 2 MFMAs, 1 load, ... — instead of being issued as one burst in front of them, so the
   // matrix pipe is never left waiting behind a queue of address computations and the loads still lead their use by
   // a whole stage.  sched_barrier(0) closes the region.
-#ifndef QPG_MPL
-#define QPG_MPL 2
-#endif
+#define QPG_MPL 2         // MFMAs named in front of every load of a stage
 #define QPG_AUDIO_STAGE(LOADSTMT, MMASTMT)                                   \
   LOADSTMT;                                                                  \
   MMASTMT;                                                                   \
@@ -268,12 +261,7 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
 // product first and, when still closer than the near-tie eps, in the reference's own arithmetic.  Operand products
 // that underflow f32 would break the bound: a pair with 0 < |q||c| < 1e-16 raises stats[1] |= 2.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef QPG_MX_PROBE
-#define QPG_MX_PROBE 0     // experiments/audio_mx ablations (results wrong): 1 = no candidate loads, 2 = no query loads,
-#endif                     // 4 = no f64 flush
-#ifndef QPG_MX_OCC
 #define QPG_MX_OCC 1      // waves per SIMD the register allocation is held to
-#endif
 template <int S>
 struct MxIC {
   static constexpr int value = S;
@@ -333,11 +321,6 @@ __device__ __forceinline__ void mx_ksplit_body(
     f32x4 b[NT][2];
   };
   auto loadA = [&](BufA& u, int e0, int tap) {
-    if (QPG_MX_PROBE & 1) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) u.a[mt][0] = u.a[mt][1] = (f32x4){1.f, 1.f, 1.f, 1.f};
-      return;
-    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const bool ok = at0[mt] + tap * tap_stride < T;          // padded taps read the zero page (see the f64 kernel)
@@ -358,11 +341,6 @@ __device__ __forceinline__ void mx_ksplit_body(
     }
   };
   auto loadB = [&](BufB& u, int e0, int tap) {
-    if (QPG_MX_PROBE & 2) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) u.b[nt][0] = u.b[nt][1] = (f32x4){1.f, 1.f, 1.f, 1.f};
-      return;
-    }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const float* p = brow[nt] + tap * F + e0;
@@ -381,7 +359,7 @@ __device__ __forceinline__ void mx_ksplit_body(
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
             f32x4 cin = acc[mt][nt];
-            if (h == 0 && i == 0 && !(QPG_MX_PROBE & 4)) {
+            if (h == 0 && i == 0) {
 #pragma unroll
               for (int r = 0; r < 4; ++r) sum[mt][nt][r] += (double)cin[r];
               cin = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -411,9 +389,7 @@ __device__ __forceinline__ void mx_ksplit_body(
   for (int d = 0; d < BD - 1; ++d) loadB(rb[d], eof((d / 6) % ne), d % 6);
 #pragma unroll
   for (int d = 0; d < AD - 1; ++d) loadA(ra[d], eof((d / 6) % ne), d % 6);
-#ifndef QPG_MX_MPL
-#define QPG_MX_MPL 2
-#endif
+#define QPG_MX_MPL 2      // MFMAs named in front of every load of a stage
   for (int s0 = 0; s0 < nst; s0 += L) {
     const int g0 = s0 / 6;
     auto stage = [&](auto jc) {
@@ -498,19 +474,14 @@ __global__ __launch_bounds__(64 * KS * GS, QPG_MX_OCC) void audio_cosine_mx_kern
 // ---------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* mx_lds_ptr_t;
 typedef __attribute__((address_space(1))) const void* mx_gbl_ptr_t;
-#ifndef QPG_MX2_OCC
-#define QPG_MX2_OCC 2
-#endif
-#ifndef QPG_MX2_PROBE
-#define QPG_MX2_PROBE 0    // experiments/audio_mx timing ablations (results wrong): 1 no barrier, 2 no candidate loads,
-#endif                     // 4 no LDS-DMA, 8 no f64 flush, 16 no fragment reads
+#define QPG_MX2_OCC 2     // waves per SIMD the register allocation is held to
 // row -> XOR applied to the 16-byte slot index of its 256-byte LDS row.  A ds_read_b128 lane group is 16 rows, eight
 // of them ({0-3,12-15} or {4-11}) at k-quarter kq and the other eight at kq^1, all reading sub-piece 4*i + kq: with
 // slot = piece ^ row both eights land on disjoint slot sets ({4..11} is closed under ^1), i.e. conflict-free.
 __device__ __forceinline__ int mx2_g(int r) { return r; }
 
 // F64 = true: the SAME organisation on the f64 matrix cores (v_mfma_f64_16x16x4_f64, operands widened in registers, no
-// chains to cut): the f64 sweep of qpg_audio_cosine_f64 for whole rounds of blocks.
+// chains to cut).  No launch instantiates it: for the f64 sweep it measured no faster than split-K (see audio_cosine()).
 template <int NT, int NTAPS, bool F64, bool HALF>
 __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
     const float* __restrict__ base, int N, int T, int F, const int32_t* __restrict__ cand_t, int G, int tap_stride,
@@ -627,18 +598,16 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
     constexpr int jj = decltype(jc)::value;
     const int s = s0 + jj;
     f32x4 (&a)[4] = ra[jj % 3];
-    if (!(QPG_MX2_PROBE & 1)) {
-      // queue, oldest first: A(s) | DMA(s) x3 | A(s+1) x4 (x2 from an f16 base): the tile of this stage has landed
-      // once no more than the A(s+1) loads are outstanding
-      if (HALF) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                // stage s landed for every wave; every wave is done with stage s-1
-    }
+    // queue, oldest first: A(s) | DMA(s) x3 | A(s+1) x4 (x2 from an f16 base): the tile of this stage has landed
+    // once no more than the A(s+1) loads are outstanding
+    if (HALF) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                  // stage s landed for every wave; every wave is done with stage s-1
     __builtin_amdgcn_sched_barrier(0);
     const int sn = s + 1 < nst ? s + 1 : 0;        // (the last prefetches wrap to valid addresses, unused)
     const int sa = s + 2 < nst ? s + 2 : s + 2 - nst;
-    if (!(QPG_MX2_PROBE & 4)) issue_b(sn, (s + 1) & 1);
-    if (!(QPG_MX2_PROBE & 2)) load_a(ra[(jj + 2) % 3], sa);
+    issue_b(sn, (s + 1) & 1);
+    load_a(ra[(jj + 2) % 3], sa);
     __builtin_amdgcn_sched_barrier(0);             // the prefetches stay in front of the stage's matrix work
     const unsigned char* S = &ring[s & 1][0];
     f32x4 b0[NT][2], b1[NT][2];
@@ -646,13 +615,7 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          if (QPG_MX2_PROBE & 16) {
-            b[nt][i] = (f32x4){1.f + nt, 2.f + i, 3.f, 4.f};
-            continue;
-          }
-          b[nt][i] = *reinterpret_cast<const f32x4*>(S + nt * 16 * ROWB + boff[2 * half + i]);
-        }
+        for (int i = 0; i < 2; ++i) b[nt][i] = *reinterpret_cast<const f32x4*>(S + nt * 16 * ROWB + boff[2 * half + i]);
     };
     auto mma_half = [&](const f32x4 (&b)[NT][2], int half) {
 #pragma unroll
@@ -667,7 +630,7 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
               continue;
             }
             f32x4 cin = acc[nt];
-            if (i == 0 && e == 0 && !(QPG_MX2_PROBE & 8)) {   // a 32-product chain is complete: into the f64 sum
+            if (i == 0 && e == 0) {   // a 32-product chain is complete: into the f64 sum
 #pragma unroll
               for (int r = 0; r < 4; ++r) sum[nt][r] += (double)cin[r];
               cin = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -715,18 +678,10 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
   }
 }
 
-#ifndef QPG_MX_AD
-#define QPG_MX_AD 2
-#endif
-#ifndef QPG_MX_BD
-#define QPG_MX_BD 2
-#endif
-#ifndef QPG_MX_KS
+#define QPG_MX_AD 2      // depth of the candidate-operand register ring
+#define QPG_MX_BD 2      // depth of the query-operand register ring
 #define QPG_MX_KS 4      // contraction slices (waves) per candidate group
-#endif
-#ifndef QPG_MX_GS
 #define QPG_MX_GS 1      // candidate groups per block
-#endif
 template <int MT, int NT>
 static int launch_audio_mx(qpg_ctx* ctx, void* stream, const float* base, bool half, int N, int T, int F,
                            const int32_t* cand_t, int G, int tap_stride, const double* cn2, const float* q32,
@@ -734,7 +689,7 @@ static int launch_audio_mx(qpg_ctx* ctx, void* stream, const float* base, bool h
                            int64_t c_end, int d_f32) {
   constexpr int KS = QPG_MX_KS, GS = QPG_MX_GS;
   dim3 grid((unsigned)((c_end - c_begin + 16 * MT * GS - 1) / (16 * MT * GS)), (unsigned)qtiles_y);
-  constexpr int AD = (QPG_MX_AD == 4) ? 3 : QPG_MX_AD;     // (a depth-4 ring needs an even feature-group count)
+  constexpr int AD = QPG_MX_AD;
   if (half)
     hipLaunchKernelGGL((audio_cosine_mx_kernel<MT, NT, 6, KS, GS, AD, QPG_MX_BD, true>), grid, dim3(64 * KS * GS), 0,
                        qpg_stream(stream), base, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD,
@@ -761,12 +716,6 @@ static int launch_audio_mx_q(qpg_ctx* ctx, void* stream, const float* base, bool
 #undef QPG_MX_ARGS
 }
 
-#ifndef QPG_MX_ORG
-#define QPG_MX_ORG 2       // 2: query tile through LDS (mx2) + split-K remainder; 1: split-K only (experiments)
-#endif
-#ifndef QPG_MX_TAIL_RIDES
-#define QPG_MX_TAIL_RIDES 1   // 1: the split-K remainder blocks are appended to the mx2 launch; 0: a launch of their own
-#endif
 static int audio_cosine_mx(const char* name, qpg_ctx* ctx, void* stream, const float* base, bool half, int N, int T, int F,
                            const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
                            const double* qn2, int Q, void* D_, int64_t ldD, int32_t* stats, int d_f32) {
@@ -784,15 +733,13 @@ static int audio_cosine_mx(const char* name, qpg_ctx* ctx, void* stream, const f
   // remaining candidates to split-K blocks of ONE 16-candidate tile (4 waves share it), which balance to a tile per CU.
   const int ny = (Q + 47) / 48;
   const int64_t nbx = C / 64;
-  int64_t main_x = 0;
-  if (QPG_MX_ORG == 2) {
-    if (ny >= 4) main_x = nbx;
-    else main_x = (nbx * ny / ctx->n_cu) * ctx->n_cu / ny;
-  }
+  int64_t main_x;
+  if (ny >= 4) main_x = nbx;
+  else main_x = (nbx * ny / ctx->n_cu) * ctx->n_cu / ny;
   const int64_t c_mid = main_x * 64;
   const int64_t tail_tiles = (C - c_mid + 15) / 16;
   // a short remainder rides in the SAME launch (blocks main_x .. main_x + tail_tiles - 1: split-K, one tile each)
-  const bool ride = main_x > 0 && tail_tiles > 0 && tail_tiles <= 4 * (int64_t)ctx->n_cu && ny == 1 && QPG_MX_TAIL_RIDES;
+  const bool ride = main_x > 0 && tail_tiles > 0 && tail_tiles <= 4 * (int64_t)ctx->n_cu && ny == 1;
   if (main_x > 0) {
     dim3 grid((unsigned)(main_x + (ride ? tail_tiles : 0)), (unsigned)ny);
     if (half)
@@ -806,7 +753,7 @@ static int audio_cosine_mx(const char* name, qpg_ctx* ctx, void* stream, const f
     QPG_LAUNCH_CHECK("audio_cosine_mx2_kernel");
   }
   if (c_mid == C || ride) return QPG_OK;
-  if (QPG_MX_ORG == 2 && tail_tiles * ny <= 4 * (int64_t)ctx->n_cu)
+  if (tail_tiles * ny <= 4 * (int64_t)ctx->n_cu)
     return launch_audio_mx_q<1>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, stats,
                                 c_mid, C, d_f32);
   return launch_audio_mx_q<2>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, stats, c_mid,
@@ -860,12 +807,9 @@ static int launch_audio_q(qpg_ctx* ctx, void* stream, const void* base, bool hal
 #undef QPG_AUDIO_ARGS
 }
 
-// 1 (default): split-K only.  2: LDS-shared-query blocks (mx2<F64>) for whole rounds + split-K remainder — correct (the
-// whole GPU suite passes with it) but NOT faster for f64: at 64 cycles per MFMA the split-K kernel is already at the
-// matrix pipe's pace (MI355X: 594 vs 590 us at Q = 48, 0.83 vs 0.81 of the roof at Q = 768, 0.79 vs 0.76 ms per step).
-#ifndef QPG_F64_ORG
-#define QPG_F64_ORG 1
-#endif
+// Split-K blocks throughout.  The LDS-shared-query organisation of the mixed sweep (mx2<F64>) for whole rounds of blocks was
+// NOT faster for f64: at 64 cycles per MFMA the split-K kernel is already at the matrix pipe's pace (MI355X: 594 vs 590 us
+// at Q = 48, 0.83 vs 0.81 of the roof at Q = 768, 0.79 vs 0.76 ms per step).
 static int audio_cosine(const char* name, qpg_ctx* ctx, void* stream, const void* base, bool half, int N, int T, int F,
                         const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
                         const double* qn2, int Q, double* D, int64_t ldD) {
@@ -877,24 +821,7 @@ static int audio_cosine(const char* name, qpg_ctx* ctx, void* stream, const void
   }
   if (N == 0 || Q == 0) return QPG_OK;
   const int64_t C = (int64_t)N * G;
-  // same work split as qpg_audio_cosine_mx (f32 base only: the f16 base keeps the split-K kernel throughout)
-  const int ny = (Q + 47) / 48;
-  const int64_t nbx = C / 64;
-  int64_t main_x = 0;
-  if (QPG_F64_ORG == 2 && !half) main_x = ny >= 4 ? nbx : (nbx * ny / ctx->n_cu) * ctx->n_cu / ny;
-  const int64_t c_mid = main_x * 64;
-  if (main_x > 0) {
-    dim3 grid((unsigned)main_x, (unsigned)ny);
-    hipLaunchKernelGGL((audio_cosine_mx2_kernel<3, 6, true, false>), grid, dim3(256), 0, qpg_stream(stream),
-                       static_cast<const float*>(base), N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD,
-                       (const float*)ctx->zeros, (int32_t*)nullptr, (int64_t)0, c_mid, (int)main_x, c_mid, 0);
-    QPG_LAUNCH_CHECK("audio_cosine_mx2_kernel<f64>");
-  }
-  if (c_mid == C) return QPG_OK;
-  const int64_t tail_tiles = (C - c_mid + 15) / 16;
-  if (main_x > 0 && tail_tiles * ny <= 4 * (int64_t)ctx->n_cu)
-    return launch_audio_q<1>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, c_mid, C);
-  return launch_audio_q<2>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, c_mid, C);
+  return launch_audio_q<2>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, 0, C);
 }
 
 extern "C" int qpg_audio_cosine_f64(qpg_ctx* ctx, void* stream, const float* base, int N, int T, int F,

@@ -62,9 +62,7 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 #define HL_QC 48              // queries per chunk
 #define HL_CT 6               // column tiles per chunk (3 lo + 3 hi)
 #define HL_GQC (16 * HL_CT)   // queries per chunk of the generic GEMM (96)
-#ifndef HL_KS
 #define HL_KS 2               // k-blocks per LDS stage
-#endif
 #define HL_PIECE 1024         // bytes of one [plane][lane][8 f16] fragment image
 
 // value of lane (l ^ PJ), PJ = 16 / 32, through gfx950's permlane swaps (qpg_common.h: lane_xor) - the GEMM epilogues'
@@ -457,12 +455,6 @@ struct HlArgs {
 
 #define HL_RING (2 * HL_KS)  // k-blocks of database fragments in flight per wave (2 KB each): two stages
 #define HL_PS (3 * HL_KS)    // pair-steps per stage
-// ablation hooks (experiments/audio_hl): -DQPG_HL_PROBE=<bits> compiles parts of the k loop out; the product build
-// defines nothing.  1: no f64 flush; 2: query fragments read from LDS once; 4: database fragments not reloaded;
-// 8: no cross-term MFMAs; 16: no query staging (loads, LDS stores, barriers) after the first stage
-#ifndef QPG_HL_PROBE
-#define QPG_HL_PROBE 0
-#endif
 
 // Block = HL_WPB database windows x 2 row tiles = 2 HL_WPB waves; wave w: window HL_WPB*blockIdx.x + (w >> 1), rows
 // 16*(w & 1) .. +15, all 96 columns of the chunk (a 16 x 96 tile of S, K = 3072).  Two waves per SIMD, <= 256 registers
@@ -481,18 +473,9 @@ struct HlArgs {
 //   the last pair-step, behind the arrival of that pair-step's own fragments: behind it nobody reads this stage's
 //   buffer any more and everybody's stores of the next stage are done, so the next stage's first fragments are
 //   prefetched under the last pair-step's MFMAs - no bubble.
-#ifndef HL_NT
-#define HL_NT 0
-#endif
-#ifndef HL_PD
-#define HL_PD 1            // pair-steps between a fragment read and its use (2 needs HL_PS %% 3 == 0 and 2 * HL_PS %% 3 == 0)
-#endif
-#ifndef HL_WPB
+#define HL_PD 1            // pair-steps between a fragment read and its use
 #define HL_WPB 4           // database windows per block (2 waves each)
-#endif
-#ifndef HL_MINW
 #define HL_MINW 2          // waves per SIMD the register allocation must leave room for
-#endif
 #define HL_THREADS (128 * HL_WPB)
 #define HL_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 // The 16-row organisation of round 3's audio sweep, kept as the plain distance GEMM over generic rows of a clip's <= 48
@@ -522,16 +505,9 @@ __global__ __launch_bounds__(HL_THREADS, HL_MINW) void hl_gemm16_kernel(HlArgs a
   const h8* dbp = row_ok ? reinterpret_cast<const h8*>(a.db) + unit0 : reinterpret_cast<const h8*>(a.zeros);
   const int pl_step = row_ok ? 64 : 0;                                   // h8 units per plane / k-block
   const int kb_step = 2 * pl_step;
-  // (HL_NT: the database image is read ONCE - a non-temporal load keeps it from evicting the query image, which every
-  // block re-reads, out of the XCD's L2)
   auto load_a = [&](int kb, h8 (&dst)[2]) {
-#if HL_NT
-    dst[0] = __builtin_nontemporal_load(dbp + (int64_t)kb * kb_step);
-    dst[1] = __builtin_nontemporal_load(dbp + (int64_t)kb * kb_step + pl_step);
-#else
     dst[0] = dbp[(int64_t)kb * kb_step];
     dst[1] = dbp[(int64_t)kb * kb_step + pl_step];
-#endif
   };
   // query image of this chunk: stage s = HL_KS*6*2 pieces of 1 KB; 16-byte units, stage_units / HL_THREADS per thread
   constexpr int stage_units = HL_KS * HL_CT * 2 * 64;
@@ -610,14 +586,12 @@ __global__ __launch_bounds__(HL_THREADS, HL_MINW) void hl_gemm16_kernel(HlArgs a
         // h h': chains of two instructions - the stage's first k-block starts them (C = 0), its second finishes them
         const f32x4 h0 = mfma_h(af[0], Bc[0][0], k2 == 0 ? zero4 : hold[c0]);
         const f32x4 h1 = mfma_h(af[0], Bc[1][0], k2 == 0 ? zero4 : hold[c0 + 1]);
-        if (!(QPG_HL_PROBE & 8)) {
-          xacc[c0] = mfma_h(af[0], Bc[0][1], xacc[c0]);         // cross terms: f32 chains (2^-11 smaller)
-          xacc[c0 + 1] = mfma_h(af[0], Bc[1][1], xacc[c0 + 1]);
-          xacc[c0] = mfma_h(af[1], Bc[0][0], xacc[c0]);
-          xacc[c0 + 1] = mfma_h(af[1], Bc[1][0], xacc[c0 + 1]);
-        }
+        xacc[c0] = mfma_h(af[0], Bc[0][1], xacc[c0]);           // cross terms: f32 chains (2^-11 smaller)
+        xacc[c0 + 1] = mfma_h(af[0], Bc[1][1], xacc[c0 + 1]);
+        xacc[c0] = mfma_h(af[1], Bc[0][0], xacc[c0]);
+        xacc[c0 + 1] = mfma_h(af[1], Bc[1][0], xacc[c0 + 1]);
         // f64 running sums: the previous pair-step's chains, if it finished any (it belonged to a stage's second k-block)
-        if (!(QPG_HL_PROBE & 1) && ((ps + HL_PS - 1) % HL_PS) / 3 == HL_KS - 1) {
+        if (((ps + HL_PS - 1) % HL_PS) / 3 == HL_KS - 1) {
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
@@ -630,7 +604,7 @@ __global__ __launch_bounds__(HL_THREADS, HL_MINW) void hl_gemm16_kernel(HlArgs a
           hp[0] = h0;
           hp[1] = h1;
         }
-        if (ps % 3 == 2 && !(QPG_HL_PROBE & 4)) {                                  // this k-block is done: refill its slot
+        if (ps % 3 == 2) {                                      // this k-block is done: refill its slot
           const int kn = kb + HL_RING < KB ? kb + HL_RING : KB - 1;
           load_a(kn, af);
         }
@@ -728,27 +702,7 @@ __device__ __forceinline__ double fast_rsqrt_f64(double x) {
   return y;
 }
 #define H2_W 8
-#ifndef H2_QFIRST
-#define H2_QFIRST 1      // the query loads go out in front of the ring's loads for every ring depth (see the k loop)
-#endif
-#ifndef H2_PIN
-#define H2_PIN 1         // two-plane kernel: where the ring's refill is issued - 0: hipcc's choice; 1: behind the stage's last
-#endif                   // MFMA; 2: two loads behind the last use of each register pair
-#ifndef H2_PRO
-#define H2_PRO 1         // prologue in the k loop's request order
-#endif
-// ablation hooks (experiments/audio_hl): -DH2_PROBE=<bits>; the product build defines nothing.  1: database fragments read
-// from one address (no HBM stream); 2: no f64 flush; 8: no stage barrier; 16: no query-fragment reads from LDS (the
-// prologue's fragments for every step); 32: no query staging (global -> register -> LDS) inside the k loop; 64: no MFMAs (the fragment loads stay)
-#ifndef H2_PROBE
-#define H2_PROBE 0
-#endif
-#ifndef H2_NT
-#define H2_NT 1          // one query chunk: the image is read ONCE - non-temporal fragment loads (round 5: the kernel with its
-#endif                   // matrix work compiled out takes 130 us with plain loads, 113 with these; 0: plain loads always)
-#ifndef H2_RS2
-#define H2_RS2 2          // stages of database fragments in flight, two-plane kernel (3 / 4: probes only - no registers)
-#endif
+#define H2_RS2 2         // stages of database fragments in flight, two-plane kernel
 // ONE-PLANE database image (round 5: the track stored in IEEE f16, GestureDB feature_dtype "f16").  An f16 value IS its
 // own h plane: no scaling (exponent 0), no l plane, no representation error on the database side - half the bytes (a
 // window is [tile 0: KB x 64 units][tile 1: KB x 44 units] of 16 bytes: 340 MB at N = 2048) and TWO products per element
@@ -784,7 +738,7 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
   const unsigned char* sbase = reinterpret_cast<const unsigned char*>(a.db) + (int64_t)jb * win_units * 16;
   const uint32_t o0 = (wj * win_units + (uint32_t)lane) * 16u;
   const uint32_t o1 = (wj * win_units + (uint32_t)KB * (64 * PL) + 11u * rg + (cg < 11 ? cg : 10)) * 16u;
-  constexpr uint32_t st0 = (H2_PROBE & 1) ? 0u : 64u * PL * 16u, st1 = (H2_PROBE & 1) ? 0u : (uint32_t)PL * HL_T1_UNITS * 16u;
+  constexpr uint32_t st0 = 64u * PL * 16u, st1 = (uint32_t)PL * HL_T1_UNITS * 16u;
   auto ld_frag = [](const unsigned char* p) -> h8 {
     if (NT) return __builtin_nontemporal_load(reinterpret_cast<const h8*>(p));
     return *reinterpret_cast<const h8*>(p);
@@ -829,19 +783,17 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
   // wait for a register is the tightest over every path into the loop, and with the query loads youngest here the loop
   // head waited vmcnt(3) for them - which drains the whole ring once per trip (round 5: 137 -> see DESIGN 4.1a).
 #pragma unroll
-  for (int i = 0; i < (H2_PRO ? 2 * (RS - 1) : 2 * RS); ++i) load_a(i, ring[i]);
+  for (int i = 0; i < 2 * (RS - 1); ++i) load_a(i, ring[i]);
   load_q(0);
   store_q(0);
   load_q(1);
   lds_barrier();
   store_q(1);
   load_q(2);
-  if (H2_PRO) {
-    __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 2 * (RS - 1); i < 2 * RS; ++i) load_a(i, ring[i]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  for (int i = 2 * (RS - 1); i < 2 * RS; ++i) load_a(i, ring[i]);
+  __builtin_amdgcn_sched_barrier(0);
   const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
   h8 B[2][2][2];                                                       // [step parity][k-block of the stage][plane]
   auto ld_b = [&](int buf, int c, h8 (&d)[2][2]) {
@@ -852,7 +804,6 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
       for (int pl = 0; pl < 2; ++pl) d[k2][pl] = qb[((k2 * HL_CT + c) * 2 + pl) * 64];
   };
   ld_b(0, 0, B[0]);
-  if (H2_PROBE & 16) ld_b(0, 1, B[1]);
   f32x4 dp[2] = {zero4, zero4};                                        // the previous step's two chains, not yet flushed
   // a trip = an even number of stages that is a multiple of RS: ring slots, LDS buffers and fragment parities are static
   constexpr int TRIP = (RS % 2 == 0) ? RS : 2 * RS;
@@ -868,19 +819,17 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
         h8 (&Bc)[2][2] = B[st & 1];
         h8 (&Bn)[2][2] = B[(st + 1) & 1];
         if (c == HL_CT - 1) {
-          if (!(H2_PROBE & 8)) lds_barrier();  // every fragment of this stage has arrived; the next stage's are stored
-          if (!(H2_PROBE & 16)) ld_b((ss + 1) & 1, 0, Bn);
-          if (!(H2_PROBE & 32) && (H2_QFIRST || RS > 2)) {
-            // vmcnt counts IN ORDER: the wait for a stage's query fragments (one stage after their request) also waits
-            // for every OLDER request.  With the query loads behind the ring's (below: the order of the two-stage ring,
-            // where it does not matter) a deeper ring buys nothing - the data of stage s + RS - 1 must be there at the
-            // end of stage s.  So here they go out FIRST (the data of stage s + RS - 2: two stages of lead for RS = 4),
-            // and a scheduling fence keeps hipcc from sinking them behind the ring's loads again (it did).
-            store_q(ss & 1);
-            load_q(s + 3);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        } else if (!(H2_PROBE & 16)) {
+          lds_barrier();                       // every fragment of this stage has arrived; the next stage's are stored
+          ld_b((ss + 1) & 1, 0, Bn);
+          // vmcnt counts IN ORDER: the wait for a stage's query fragments (one stage after their request) also waits
+          // for every OLDER request.  With the query loads behind the ring's refill (at the end of the stage) a deeper
+          // ring buys nothing - the data of stage s + RS - 1 must be there at the end of stage s.  So here they go out
+          // FIRST, for every ring depth (the data of stage s + RS - 2: two stages of lead for RS = 4), and a scheduling
+          // fence keeps hipcc from sinking them behind the ring's loads again (it did).
+          store_q(ss & 1);
+          load_q(s + 3);
+          __builtin_amdgcn_sched_barrier(0);
+        } else {
           ld_b(ss & 1, c + 1, Bn);
         }
         // two chains (row tile 0 / 1), interleaved.  ORDER INSIDE A CHAIN: the cross-term instructions first (h l', l h' of
@@ -888,38 +837,28 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
         // instructions last - the chain then behaves like round 3's chain of two (measured: every instruction that
         // re-rounds a FULL-SIZE running sum costs ~1.2-1.5 units of 2^-24 sum|products|, so h h' first would mean
         // kappa_6 = 14.4 against 9.9 this way; selfcheck.py measures this order)
-        f32x4 d0, d1;
-        if (H2_PROBE & 64) {                                       // probe: the loads and everything else, no matrix work
-#pragma unroll
-          for (int i = 0; i < 2 * PL; ++i) asm volatile("" ::"v"(A0[i]), "v"(A1[i]));
-          d0 = zero4;
-          d1 = zero4;
-        } else {
-          d0 = mfma_h(A0[0], Bc[0][1], (H2_PROBE & 2) ? dp[0] : zero4);     // (probe 2: one endless chain, no flush)
-          d1 = mfma_h(A0[PL], Bc[0][1], (H2_PROBE & 2) ? dp[1] : zero4);
-          if (PL == 2) {
-            d0 = mfma_h(A0[PL - 1], Bc[0][0], d0);
-            d1 = mfma_h(A0[2 * PL - 1], Bc[0][0], d1);
-          }
-          d0 = mfma_h(A1[0], Bc[1][1], d0);
-          d1 = mfma_h(A1[PL], Bc[1][1], d1);
-          if (PL == 2) {
-            d0 = mfma_h(A1[PL - 1], Bc[1][0], d0);
-            d1 = mfma_h(A1[2 * PL - 1], Bc[1][0], d1);
-          }
-          d0 = mfma_h(A0[0], Bc[0][0], d0);
-          d1 = mfma_h(A0[PL], Bc[0][0], d1);
-          d0 = mfma_h(A1[0], Bc[1][0], d0);
-          d1 = mfma_h(A1[PL], Bc[1][0], d1);
+        f32x4 d0 = mfma_h(A0[0], Bc[0][1], zero4);
+        f32x4 d1 = mfma_h(A0[PL], Bc[0][1], zero4);
+        if (PL == 2) {
+          d0 = mfma_h(A0[PL - 1], Bc[0][0], d0);
+          d1 = mfma_h(A0[2 * PL - 1], Bc[0][0], d1);
         }
+        d0 = mfma_h(A1[0], Bc[1][1], d0);
+        d1 = mfma_h(A1[PL], Bc[1][1], d1);
+        if (PL == 2) {
+          d0 = mfma_h(A1[PL - 1], Bc[1][0], d0);
+          d1 = mfma_h(A1[2 * PL - 1], Bc[1][0], d1);
+        }
+        d0 = mfma_h(A0[0], Bc[0][0], d0);
+        d1 = mfma_h(A0[PL], Bc[0][0], d1);
+        d0 = mfma_h(A1[0], Bc[1][0], d0);
+        d1 = mfma_h(A1[PL], Bc[1][0], d1);
         // f64 running sums: the PREVIOUS step's chains (zeros in front of the first step)
-        if (!(H2_PROBE & 2)) {
-          const int pc = (c + HL_CT - 1) % HL_CT;
+        const int pc = (c + HL_CT - 1) % HL_CT;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            acc[0][pc][r] += (double)dp[0][r];
-            acc[1][pc][r] += (double)dp[1][r];
-          }
+        for (int r = 0; r < 4; ++r) {
+          acc[0][pc][r] += (double)dp[0][r];
+          acc[1][pc][r] += (double)dp[1][r];
         }
         dp[0] = d0;
         dp[1] = d1;
@@ -928,21 +867,16 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
           // stage after next (behind the barrier above: nobody reads this stage's buffer any more)
           load_a(2 * (s + RS), A0);
           load_a(2 * (s + RS) + 1, A1);
-          if (!(H2_PROBE & 32) && !H2_QFIRST && RS <= 2) {
-            store_q(ss & 1);
-            load_q(s + 3);
-          }
         }
 #pragma unroll
         for (int i = 0; i < 4 + 4 * PL; ++i) { // issue order: an MFMA, then a fragment read / a share of the flush under it
           HL_SGB(0x008, 1);
           if (i < 4) HL_SGB(0x100, 1);
           HL_SGB(0x002, PL == 2 ? 2 : 3);
-          if (H2_PIN == 2 && PL == 2 && c == HL_CT - 1 && (i == 3 || i == 7 || i == 9 || i == 11)) HL_SGB(0x020, 2);
         }
         // the ring's refill goes out HERE, behind the stage's last MFMAs (their registers are free then) - named, or hipcc
         // issues it somewhere in the middle of the next stage and the ring loses a third of its lead
-        if (c == HL_CT - 1 && H2_PIN == 1 && PL == 2) HL_SGB(0x020, 4 * PL);
+        if (c == HL_CT - 1 && PL == 2) HL_SGB(0x020, 4 * PL);
       }
     }
   }
@@ -1141,7 +1075,9 @@ extern "C" int qpg_audio_cosine_hl(qpg_ctx* ctx, void* stream, const void* db_im
   a.KB = KB; a.d_f32 = d_is_f32; a.tmin = nullptr; a.ldT = 0; a.tmask = nullptr; a.band = 0.f; a.chunks = chunks;
   const int64_t g8 = ((int64_t)N + H2_W - 1) / H2_W;
   QPG_REQUIRE(((g8 + 7) / 8) * 8 * chunks < 0x7fffffffll, "%s: too many blocks", name);
-  const bool nt = H2_NT == 2 || (H2_NT == 1 && chunks == 1);      // several chunks re-read the image out of the XCD's L2
+  // one query chunk: the image is read ONCE - non-temporal fragment loads (round 5: the kernel with its matrix work compiled
+  // out takes 130 us with plain loads, 113 with these); several chunks re-read the image out of the XCD's L2
+  const bool nt = chunks == 1;
   void (*kern)(HlArgs) = nt ? audio_cosine_hl2_kernel<2, H2_RS2, true> : audio_cosine_hl2_kernel<2, H2_RS2, false>;
   hipLaunchKernelGGL(kern,
                      dim3((unsigned)(((g8 + 7) / 8) * 8 * chunks)), dim3(64 * H2_W), 2 * 2 * HL_CT * 2 * HL_PIECE,
@@ -1224,7 +1160,7 @@ extern "C" int qpg_audio_cosine_hl1(qpg_ctx* ctx, void* stream, const void* db_i
   a.KB = KB; a.d_f32 = d_is_f32; a.tmin = nullptr; a.ldT = 0; a.tmask = nullptr; a.band = 0.f; a.chunks = chunks;
   const int64_t g8 = ((int64_t)N + H2_W - 1) / H2_W;
   QPG_REQUIRE(((g8 + 7) / 8) * 8 * chunks < 0x7fffffffll, "%s: too many blocks", name);
-  const bool nt = H2_NT == 2 || (H2_NT == 1 && chunks == 1);
+  const bool nt = chunks == 1;                                    // (as the two-plane launch)
   void (*kern)(HlArgs) = nt ? audio_cosine_hl2_kernel<1, H1_RS, true> : audio_cosine_hl2_kernel<1, H1_RS, false>;
   hipLaunchKernelGGL(kern,
                      dim3((unsigned)(((g8 + 7) / 8) * 8 * chunks)), dim3(64 * H2_W), 2 * 2 * HL_CT * 2 * HL_PIECE,
@@ -1479,9 +1415,7 @@ extern "C" int qpg_hl_prepare_queries(qpg_ctx* ctx, void* stream, const float* q
 // NEXT stage (or of the next item's first stage): three k-blocks = 108 MFMAs per wave of lead.
 #define G32_KS 2           // k-blocks per LDS stage of the query image (24 KB)
 #define G32_RING 4         // k-blocks of row fragments in registers: two stages
-#ifndef G32_PD
 #define G32_PD 2           // steps between a column tile's fragment read and its use
-#endif
 template <int CT>
 __global__ __launch_bounds__(512, 2) void hl_gemm32_kernel(HlArgs a, int n_items) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // 2 x G32_KS x 6 x 2 x 1 KB = 48 KB
@@ -1667,15 +1601,7 @@ __global__ __launch_bounds__(512, 2) void hl_gemm32_kernel(HlArgs a, int n_items
 // ([tile][a.ldT], a.ldT >= Q: the 16 queries of a column tile are one 64-byte store; the by-code select reads a tile's
 // queries contiguously).  Needs KB % 4 == 0 (D % 128 == 0) and an even number of 32-row groups.
 #define G64_KS 4
-// ablation hooks (experiments/gemm32, experiments/round_scripts/r05_probe_gemm64.sh): -DG64_PROBE=<bits>; the product build defines nothing.
-// 1: no epilogue (the accumulators are only kept alive); 2: row fragments from one address (no row stream); 4: no query
-// staging inside the k loop; 8: no MFMAs (loads, staging and epilogue stay); 16: no query-fragment reads from LDS
-#ifndef G64_PROBE
-#define G64_PROBE 0
-#endif
-#ifndef G64_PD
 #define G64_PD 2          // steps between a column tile's fragment read and its use (3 and 5 measured: see DESIGN 4.4)
-#endif
 // PAIR: two stages per trip of the k loop, LDS buffer indices static (an even number of stages: D % 256 == 0, configs[2]);
 // !PAIR: one stage per trip, the buffer index carried in a register (any D % 128 == 0; hipcc's over-tight wait at the loop
 // head - see DESIGN.md 4.4 - is then paid per stage instead of per two)
@@ -1758,9 +1684,8 @@ __global__ __launch_bounds__(64 * NW, 2) void hl_gemm64h_kernel(HlArgs a, int n_
     r.ok = 2 * r.jj < a.N;
     r.base = r.ok ? (gbytes_t)(reinterpret_cast<const unsigned char*>(a.db) + (int64_t)r.jj * 4 * KB * 2048)
                   : (gbytes_t)reinterpret_cast<const unsigned char*>(a.zeros);
-    r.t_step = (r.ok && !(G64_PROBE & 2)) ? (uint32_t)KB * 2048u : 0u;
-    r.kb_step = (r.ok && !(G64_PROBE & 2)) ? 2048u : 0u;
-    if (G64_PROBE & 2) r.base = (gbytes_t)reinterpret_cast<const unsigned char*>(a.db);
+    r.t_step = r.ok ? (uint32_t)KB * 2048u : 0u;
+    r.kb_step = r.ok ? 2048u : 0u;
     // (pinned in scalar registers HERE: left alone, hipcc sinks this arithmetic - a division and selects, i.e. branches -
     // into the stage's basic block, next to the refill loads)
     asm volatile("" : "+s"(r.base), "+s"(r.t_step), "+s"(r.kb_step));
@@ -1787,7 +1712,6 @@ __global__ __launch_bounds__(64 * NW, 2) void hl_gemm64h_kernel(HlArgs a, int n_
   static_assert((2 * NS) % (G64_PD + 1) == 0 && NS % (G64_PD + 1) == 0, "the fragment ring index must be static");
 #pragma unroll
   for (int i = 0; i < G64_PD; ++i) ld_b(0, i / CT, i % CT, Bq[i]);
-  if (G64_PROBE & 16) ld_b(0, 0, 0, Bq[G64_PD]);
   auto epilogue = [&](const Rows& done, int chunk) {
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -1833,7 +1757,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hl_gemm64h_kernel(HlArgs a, int n_
         const int ss = PAIR ? sp : sbuf;                               // this stage's LDS buffer
         if (!PAIR) sbuf ^= 1;
         const bool last_s = s + 1 == n_stage;
-        if (!(G64_PROBE & 4)) load_q(last_s ? it_nxt.ch : it_cur.ch, last_s ? 0 : s + 1);   // in flight underneath this stage's MFMAs
+        load_q(last_s ? it_nxt.ch : it_cur.ch, last_s ? 0 : s + 1);   // in flight underneath this stage's MFMAs
         // the stage's k-blocks are refilled with the same k-blocks of the next stage - of this item, or (behind its last
         // stage) of the next item's first stage: scalars chosen HERE, so that the stage stays ONE basic block
         gbytes_t rf_base = cur.base + (uint32_t)(s + 1) * G64_KS * cur.kb_step;
@@ -1851,20 +1775,13 @@ __global__ __launch_bounds__(64 * NW, 2) void hl_gemm64h_kernel(HlArgs a, int n_
           h8& Bc = Bq[st % (G64_PD + 1)];                              // (NS % (G64_PD + 1) == 0)
           h8& Bn = Bq[(st + G64_PD) % (G64_PD + 1)];
           if (st == NS - G64_PD) {
-            if (!(G64_PROBE & 4)) store_q(ss ^ 1);
+            store_q(ss ^ 1);
             lds_barrier();
           }
-          if (!(G64_PROBE & 16)) {
-            if (st >= NS - G64_PD) ld_b(ss ^ 1, (st + G64_PD - NS) / CT, (st + G64_PD - NS) % CT, Bn);
-            else ld_b(ss, (st + G64_PD) / CT, (st + G64_PD) % CT, Bn);
-          }
-          if (G64_PROBE & 8) {
+          if (st >= NS - G64_PD) ld_b(ss ^ 1, (st + G64_PD - NS) / CT, (st + G64_PD - NS) % CT, Bn);
+          else ld_b(ss, (st + G64_PD) / CT, (st + G64_PD) % CT, Bn);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(Ac[t]), "v"(Bc));
-          } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) hh[t][c] = mfma_h(Ac[t], Bc, hh[t][c]);
-          }
+          for (int t = 0; t < 4; ++t) hh[t][c] = mfma_h(Ac[t], Bc, hh[t][c]);
           if (c == CT - 1) load_a(rf_base, rf_t, (uint32_t)k2 * rf_k, Ac);      // this k-block is done: its slot is refilled
           // issue order (every class named, or hipcc sinks the loads to their uses and waits vmcnt(0) there): the
           // stage's query loads first; per step an MFMA, the fragment read underneath it, three MFMAs; the refill's
@@ -1883,16 +1800,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hl_gemm64h_kernel(HlArgs a, int n_
     const int chunk = it_cur.ch;
     cur = nxt;
     it_cur = it_nxt;
-    if (done.ok) {
-      if (G64_PROBE & 1) {
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-          for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(hh[t][c]));
-      } else {
-        epilogue(done, chunk);
-      }
-    }
+    if (done.ok) epilogue(done, chunk);
     if (!more) break;                        // (that was the last item)
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // surplus prefetches must not outlive their registers

@@ -33,15 +33,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 #define C16_BN 128          // output channels per block
 #define C16_BK 32           // contraction slice
 #define C16_SLICE_BYTES 16384   // one operand's slice: 8 tiles x 2 planes x 1 KB
-// ablation hooks (experiments/round_scripts/r05_probe_conv16.sh): -DC16_PROBE=<bits>; the product build defines nothing.  1: no MFMAs; 2: no
-// split + LDS stores in the loop; 4: no global requests in the loop; 8: no fragment reads from LDS; 16: no slice barrier;
-// 32: the activation requests of a wave coalesced into one 2 KB run (timing only: wrong values)
-#ifndef C16_PROBE
-#define C16_PROBE 0
-#endif
-#ifndef C16_SGB
-#define C16_SGB 5          // VALU operations named behind every MFMA of a slice (0: hipcc's own order)
-#endif
 
 struct Conv16Args {
   const float* x;          // [B][T_in][Cx] channels-last, Cx % 8 == 0
@@ -97,8 +88,6 @@ __global__ __launch_bounds__(256, 2) void conv1d_hl_kernel(Conv16Args a) {
       const int t_c = t_in < 0 ? 0 : (t_in < a.T_in ? t_in : a.T_in - 1);
       const int c_c = c0 + 8 <= a.Cx ? c0 : a.Cx - 8;
       const f32x4* p = reinterpret_cast<const f32x4*>(a.x + ((int64_t)sb[i] * a.T_in + t_c) * a.Cx + c_c);
-      if (C16_PROBE & 32)     // TIMING ONLY (wrong values): the wave's 64 pieces of 32 bytes as ONE contiguous 2 KB run
-        p = reinterpret_cast<const f32x4*>(a.x + ((int64_t)sb[0] * a.T_in) * a.Cx + (int64_t)(s & 7) * 4096 + w * 1024 + i * 512 + lane * 8);
       xr[i][0] = p[0];
       xr[i][1] = p[1];
     }
@@ -149,17 +138,13 @@ __global__ __launch_bounds__(256, 2) void conv1d_hl_kernel(Conv16Args a) {
     // slice s is in buffer s & 1; buffer (s + 1) & 1 was last read in slice s - 1.  An LDS-only barrier: the global loads
     // of the slice after next stay in flight across it (__syncthreads() is s_waitcnt vmcnt(0) first)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(C16_PROBE & 16)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     const int buf = s & 1;
     const h8* wl = reinterpret_cast<const h8*>(lds + buf * 2 * C16_SLICE_BYTES) + lane;
     const h8* xl = reinterpret_cast<const h8*>(lds + buf * 2 * C16_SLICE_BYTES + C16_SLICE_BYTES) + lane;
     h8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if ((C16_PROBE & 8) && s > 0) {
-        asm volatile("" : "=v"(ah[i]), "=v"(al[i]), "=v"(bh[i]), "=v"(bl[i]));
-        continue;
-      }
       ah[i] = wl[((4 * wn + i) * 2 + 0) * 64];
       al[i] = wl[((4 * wn + i) * 2 + 1) * 64];
       bh[i] = xl[((4 * wm + i) * 2 + 0) * 64];
@@ -171,33 +156,26 @@ __global__ __launch_bounds__(256, 2) void conv1d_hl_kernel(Conv16Args a) {
     // address arithmetic of the requests can be issued UNDERNEATH the 48 MFMAs instead of in front of them (round 5, last
     // hours: hipcc had left the four phases - fragment reads, split + stores, requests, MFMAs - one after the other;
     // with two waves per SIMD the matrix pipe idled half the time).
-    if (!(C16_PROBE & 2)) commit(buf ^ 1);
-    if (!(C16_PROBE & 4)) fetch(s + 2 < n_slice ? s + 2 : n_slice - 1);
-    if (C16_PROBE & 1) {
+    commit(buf ^ 1);
+    fetch(s + 2 < n_slice ? s + 2 : n_slice - 1);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(ah[i]), "v"(al[i]), "v"(bh[i]), "v"(bl[i]));
-    } else {
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] = mfma16h(ah[i], bl[j], acc[i][j]);
-          acc[i][j] = mfma16h(al[i], bh[j], acc[i][j]);
-          acc[i][j] = mfma16h(ah[i], bh[j], acc[i][j]);
-        }
-    }
-#if C16_SGB
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = mfma16h(ah[i], bl[j], acc[i][j]);
+        acc[i][j] = mfma16h(al[i], bh[j], acc[i][j]);
+        acc[i][j] = mfma16h(ah[i], bh[j], acc[i][j]);
+      }
     // issue order: the 16 fragment reads up front (the first MFMAs need them), then per MFMA a few VALU operations of the
     // split; the LDS stores and the requests spread over the MFMAs behind the conversions that feed them
 #pragma unroll
     for (int i = 0; i < 48; ++i) {
       if (i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, C16_SGB, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);        // 5 VALU operations named behind every MFMA
       if (i >= 16 && (i & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       if (i >= 32 && (i & 1) == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     }
-#endif
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the surplus request must not outlive its registers)
   if (bad && a.status) atomicOr(a.status, 1);

@@ -470,9 +470,7 @@ extern "C" int qpg_percode_select_guarded_f64(qpg_ctx* ctx, void* stream, const 
 // ---------------------------------------------------------------------------------------------------------------
 #define MIX_LIST 2048
 #define MIX_LIST2 256
-#ifndef MIX_POT
 #define MIX_POT 6144    // candidates that were within the band of their code's minimum SO FAR when pass 1 visited them
-#endif                  // (-DMIX_POT=64 makes every test take the overflow path: verified once, experiments/audio_mx/README.md)
 
 // f64 dot product of (query q, local candidate c) by one wave; every lane returns the sum.  F % 256 == 0 (the WavLM
 // width) and n_taps == 6: a lane owns the 16-byte piece lane + 64*j of every tap; ALL candidate loads of the pair
@@ -543,9 +541,6 @@ __device__ __forceinline__ double pair_dot_wave_f64(const GuardArgs& A, int q, i
 //                   (P = MIX_SPLIT x MIX_SPOT: slice s owns entries [s MIX_SPOT, (s + 1) MIX_SPOT) - no global counter)
 // The streamed states are ALL-ZERO between launches (the list kernel resets what it consumes; offsets do not depend on
 // Q): the caller zero-fills the workspace once.
-#ifndef MIX_INV_ATOMIC
-#define MIX_INV_ATOMIC 0  // 1 (A/B builds only): round 5's merge of the slices' minima - atomicMax into one shared row
-#endif
 #define MIX_SPLIT 8       // blocks per query streaming the row
 #define MIX_SPOT 3072     // potential band members a slice can hold in LDS
 #define MIX_GPOT (MIX_SPLIT * MIX_SPOT)
@@ -580,26 +575,6 @@ __host__ __device__ __forceinline__ MixStream mix_stream_of(unsigned char* ws, i
 }
 
 
-// -DQPG_SELECT_PROF (experiments/select_prof): block 0 stamps the 100 MHz wall clock at the section boundaries of the
-// mixed select; qpg_debug_select_prof copies the stamps out.  Not in the product build (-DQPG_SELECT_PROF implies a
-// hooks build: experiments/select_prof/build.sh).
-#ifdef QPG_SELECT_PROF
-__device__ long long qpg_select_prof_buf[6][16];      // [phase]: wall clock; [3 + phase]: shader clock (s_memtime)
-#define SEL_STAMP(i)                                                                          \
-  do {                                                                                        \
-    __syncthreads();                                                                          \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {                             \
-      qpg_select_prof_buf[phase][i] = wall_clock64();                                         \
-      qpg_select_prof_buf[3 + phase][i] = clock64();                                          \
-    }                                                                                         \
-  } while (0)
-extern "C" int qpg_debug_select_prof(long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(qpg_select_prof_buf), sizeof(long long) * 96) == hipSuccess ? 0 : -1;
-}
-#else
-#define SEL_STAMP(i)
-#endif
-
 // Tier-1 dot products of every query's list, on the whole GPU: grid (Q, RB), 4 waves per block, wave g of the 4 RB of a
 // query takes list entries g, g + 4 RB, ...  RB = 64 at Q = 48: 256 waves per query, one pair each for any list up to 256
 // entries (round 2 gave a query 64 waves: the longest list, ~150 entries, took three rounds of ~12 us - a pair is 24 KB of
@@ -631,7 +606,7 @@ __global__ __launch_bounds__(256) void select_refine_kernel(GuardArgs A, int K, 
 // 21 us on the row's 320 KB, with 48 of the 256 CUs busy).  Block (q, s) streams slice s of row q: per-code minimum in
 // LDS (4-byte keys), the candidates within eps1 of their code's minimum SO FAR remembered; at the end those still within
 // eps1 of the slice's FINAL minimum are appended to the query's list in the workspace (candidate, value, code) and the
-// slice's minima merged into the query's table (atomicMax of the inverted key).  The list kernel (phase 1 of
+// slice's minima stored as the slice's own row of the query's table (inverted keys).  The list kernel (phase 1 of
 // percode_select_mixed_f64_kernel, `pre` set) starts from that state instead of streaming.
 __global__ __launch_bounds__(1024) void mixed_stream_kernel(const float* __restrict__ D, int64_t ldD,
                                                            const int16_t* __restrict__ cand_code, int64_t C, int K,
@@ -643,9 +618,6 @@ __global__ __launch_bounds__(1024) void mixed_stream_kernel(const float* __restr
   int16_t* pk = reinterpret_cast<int16_t*>(pd + MIX_SPOT);                              // [MIX_SPOT]
   __shared__ int n_pot, n_keep;
   const int q = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
-#ifdef QPG_SELECT_PROF
-  const int phase = 0;
-#endif
   const float* row = D + (int64_t)q * ldD;
   const int64_t chunk = (((C + MIX_SPLIT - 1) / MIX_SPLIT) + 63) & ~(int64_t)63;
   const int64_t c0 = (int64_t)sl * chunk, c1 = c0 + chunk < C ? c0 + chunk : C;
@@ -655,7 +627,6 @@ __global__ __launch_bounds__(1024) void mixed_stream_kernel(const float* __restr
     n_keep = 0;
   }
   __syncthreads();
-  SEL_STAMP(0);
   auto visit = [&](int64_t c, float dv, int cd) {
     if ((unsigned)cd >= (unsigned)K) return;
     const unsigned int key = order_key(dv);
@@ -722,15 +693,8 @@ __global__ __launch_bounds__(1024) void mixed_stream_kernel(const float* __restr
   }
   for (int64_t c = cv + tid; c < c1; c += blockDim.x) visit(c, row[c], cand_code[c]);
   __syncthreads();
-  SEL_STAMP(1);
   MixStream m = mix_stream_of(ws, q, K);
-  if (MIX_INV_ATOMIC) {
-    for (int k = tid; k < K; k += blockDim.x)
-      if (best32[k] != 0xffffffffu) atomicMax(&m.inv[k], ~best32[k]);
-  } else {
-    for (int k = tid; k < K; k += blockDim.x) m.inv[(size_t)sl * K + k] = ~best32[k];     // (0: no candidate in this slice)
-  }
-  SEL_STAMP(2);
+  for (int k = tid; k < K; k += blockDim.x) m.inv[(size_t)sl * K + k] = ~best32[k];       // (0: no candidate in this slice)
   const int np = n_pot;
   if (np > MIX_SPOT) {                        // the list kernel then streams the row itself (its own fallback)
     if (tid == 0) m.cnt[sl] = -1;
@@ -748,7 +712,6 @@ __global__ __launch_bounds__(1024) void mixed_stream_kernel(const float* __restr
   }
   __syncthreads();
   if (tid == 0) m.cnt[sl] = n_keep;
-  SEL_STAMP(3);
 }
 
 template <typename DT>
@@ -799,7 +762,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   }
   if (tid < 8) ctl[tid] = 0;
   __syncthreads();
-  SEL_STAMP(0);
   // rank of every code in the value table v (stable: value, then code); s_code[r] = code at rank r
   // (sorted, not counted: block_sorted_ranks; its scratch aliases p_c / p_k, which are dead once list (a) is built)
   unsigned long long* skey = reinterpret_cast<unsigned long long*>(p_c);      // [512] (K <= 512: 6 KB of p_c | p_k's 12)
@@ -875,10 +837,7 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   if (K32) {
     for (int k = tid; k < K; k += blockDim.x) {
       unsigned int b;
-      if (streamed && MIX_INV_ATOMIC) {
-        b = ~ms.inv[k];
-        ms.inv[k] = 0;                        // (left all-zero for the next launch)
-      } else if (streamed) {
+      if (streamed) {
         unsigned int iv[MIX_SPLIT], mx = 0u;  // the slices' rows: independent loads, one round trip
 #pragma unroll
         for (int sl = 0; sl < MIX_SPLIT; ++sl) iv[sl] = ms.inv[(size_t)sl * K + k];
@@ -899,7 +858,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     }
     __syncthreads();
   }
-  SEL_STAMP(1);
   auto pass2 = [&](int64_t c, double d, int cd) {
     if ((unsigned)cd >= (unsigned)K) return;
     const unsigned long long bk = best[cd];
@@ -965,7 +923,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   }
   __syncthreads();
   if (streamed && tid < MIX_SPLIT) ms.cnt[tid] = 0;            // (left all-zero for the next launch)
-  SEL_STAMP(2);
   for (int k = tid; k < K; k += blockDim.x) v[k] = besti[k] != 0xffffffffu ? key_value(best[k], 0.0) : absent;
   __syncthreads();
   // ---- walk-relevance cut (RankCut; streamed f32 path with ranks only).  With E the sweep's bound (eps1 >= 2 E), a
@@ -997,7 +954,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     // this order + a local repair instead of a second sort of the 512 values)
     for (int r = tid; r < K; r += blockDim.x) reinterpret_cast<int16_t*>(wq + mix_park_order_off(K))[r] = (int16_t)s_code[r];
     order_parked = true;
-    SEL_STAMP(13);
     for (int r = tid; r < K; r += blockDim.x) {
       const int k = s_code[r];
       int b = 0, a = 0;
@@ -1009,7 +965,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       hi_[k] = (int16_t)(r + a);
     }
     __syncthreads();
-    SEL_STAMP(14);
     // the probe codes' constants in LDS, then every previous code p takes its column entries of the probe codes: thread
     // (p, half) reads 32 of the (at most 64) entries with 32 INDEPENDENT loads in flight - a loop of dependent round trips,
     // one per probe code, cost 28 us here - and the two halves meet in LDS
@@ -1082,7 +1037,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     }
     __syncthreads();
     const double umax = red[16];
-    SEL_STAMP(15);
     for (int k = tid; k < K; k += blockDim.x) need[k] = (besti[k] != 0xffffffffu && (double)lo_[k] <= umax) ? 1 : 0;
     __syncthreads();
     for (int r = tid; r < K; r += blockDim.x) {
@@ -1121,7 +1075,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     }
   }
   __syncthreads();
-  SEL_STAMP(3);
   // ---- list (b): winners of codes whose minima lie within eps1 of ANOTHER code's (only needed when ranks are wanted:
   // without them the minima of different codes are never compared here).  Two values that close are rank neighbours, but
   // finding them does not need the ranks (a sort: 14 us here): every present code drops its value into a grid of cells
@@ -1144,7 +1097,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       }
     }
     __syncthreads();
-    SEL_STAMP(4);
   } else if (out_rank) {
     unsigned int* cell = reinterpret_cast<unsigned int*>(p_c);          // [2048] (p_c / p_k are dead: list (a) is built)
     const double inv_w = 1.0 / (eps1 * 1.000001);
@@ -1183,7 +1135,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       }
     }
     __syncthreads();
-    SEL_STAMP(4);
   }
   n = ctl[0];
   if (n > MIX_LIST) {
@@ -1191,7 +1142,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     if (tid == 0) atomicOr(&A.stats[1], 1);
   }
   }   // phase != 2
-  SEL_STAMP(5);
   if (phase == 1) {            // park: [best u64 K][v f64 K][besti u32 K][near u32 K][n, pad][l_c i32 L][l_k i32 L][l_d f64 L]
     unsigned long long* w_best = reinterpret_cast<unsigned long long*>(wq);
     double* w_v = reinterpret_cast<double*>(wq + 8 * (size_t)K);
@@ -1214,7 +1164,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       w_n[0] = n;
       w_n[1] = order_parked ? 1 : 0;         // the parked order is this launch's
     }
-    SEL_STAMP(6);
     return;
   }
   if (phase == 2) {
@@ -1246,7 +1195,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     }
     __syncthreads();
   }
-  SEL_STAMP(7);
   if (n > 0) {
     // ---- tier 1: f64 dot products, one wave per listed pair (phase 2: already done by select_refine_kernel)
     const double qq = qn2[q];
@@ -1329,7 +1277,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
     out_dist[(int64_t)q * K + k] = v[k];
     out_idx[(int64_t)q * K + k] = have ? (int32_t)besti[k] : -1;
   }
-  SEL_STAMP(8);
   if (!out_rank) return;
   if (tid == 0) ctl[2] = 0;
   __syncthreads();
@@ -1364,7 +1311,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       for (int r = tid; r < K; r += blockDim.x) out_rank[(int64_t)q * K + s_code[r]] = (int16_t)r;
   }
   if (!repaired) rank_pass(true);
-  SEL_STAMP(9);
   if (A.eps <= 0.0) return;
   __syncthreads();
   // ---- tier 2 (rank level): refined minima of different codes within eps2 -> reference arithmetic for their winners
@@ -1389,7 +1335,6 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   }
   __syncthreads();
   int n3 = ctl[2];
-  SEL_STAMP(10);
   if (n3 == 0) return;
   if (n3 > MIX_LIST2) {
     n3 = MIX_LIST2;
@@ -1406,9 +1351,7 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   }
   if (tid == 0) atomicAdd(&A.stats[0], n3);
   __syncthreads();
-  SEL_STAMP(11);
   rank_pass(true);
-  SEL_STAMP(12);
 }
 
 extern "C" int64_t qpg_percode_select_mixed_ws_bytes(int Q, int K) {

@@ -514,15 +514,8 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_mfma_kernel(WgradArgs a) {
     ft = ht;
   };
 
-  // ablation hooks (experiments/conv_probe): -DQPG_WGRAD_PROBE=n compiles parts of the chunk loop out; the product build
-  // defines nothing.  1: no global prefetch after the first chunk; 2: and no commit / barriers; 3: MFMAs on constant
-  // registers; 4: as 3, and the partial tile is not stored.
-#ifndef QPG_WGRAD_PROBE
-#define QPG_WGRAD_PROBE 0
-#endif
   if (r_begin < r_end) fetch();
   for (int64_t r0 = r_begin; r0 < r_end; r0 += WG_BK) {
-#if QPG_WGRAD_PROBE < 2
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < RH; ++h) {
@@ -543,16 +536,9 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_mfma_kernel(WgradArgs a) {
       }
     }
     __syncthreads();
-#endif
-#if QPG_WGRAD_PROBE < 1
     if (r0 + WG_BK < r_end) fetch();
-#endif
     float aq[2][2], bq[2][2];
     auto lds_read = [&](int ks, int slot) {
-#if QPG_WGRAD_PROBE >= 3
-      aq[slot][0] = aq[slot][1] = bq[slot][0] = bq[slot][1] = 1.0f;
-      return;
-#endif
       const int k = ks * 2 + (lane >> 5);
       aq[slot][0] = Xs[k][wm * 64 + (lane & 31)];
       aq[slot][1] = Xs[k][wm * 64 + 32 + (lane & 31)];
@@ -581,9 +567,6 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_mfma_kernel(WgradArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ci = ci0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-#if QPG_WGRAD_PROBE >= 4
-        if (acc[i][j][r] != 12345.678f) continue;
-#endif
         if (ci < a.Cin_pad) wsz[(int64_t)ci * a.Cout_pad + co] = acc[i][j][r];
       }
     }

@@ -133,9 +133,6 @@ __global__ __launch_bounds__(256, MT == 2 ? 4 : 2) void conv1d_mfma_f32_kernel(C
       }
     }
     const float* wp = WT ? w_tap + c0 : w_tap + (int64_t)c0 * a.Cout_pad;
-#if defined(QPG_CONV_PROBE) && QPG_CONV_PROBE == 5      // probe: the weight tile comes from the zero page (one hot line)
-    wp = a.zeros;
-#endif
     b0 = *reinterpret_cast<const f32x4*>(wp);
     b1 = *reinterpret_cast<const f32x4*>(wp + 4);
     if (WT && !w_ok) okm = 0x80000000u;
@@ -182,22 +179,13 @@ __global__ __launch_bounds__(256, MT == 2 ? 4 : 2) void conv1d_mfma_f32_kernel(C
   }
   for (int it = it0; it < it1; ++it) {
     constexpr int buf = 0;
-#if !defined(QPG_CONV_PROBE) || QPG_CONV_PROBE == 1
     __syncthreads();   // previous slice fully consumed
     commit(buf);
     __syncthreads();
-#endif
-#if !defined(QPG_CONV_PROBE)
     if (it + 1 < it1) fetch();           // in flight during the MFMAs below
-#endif
     // LDS operand reads run one k-pair ahead of the MFMAs that consume them
     float bq[2][2], aq[2][MT];
     auto lds_read = [&](int ks, int slot) {
-#if defined(QPG_CONV_PROBE) && QPG_CONV_PROBE >= 3
-      bq[slot][0] = bq[slot][1] = 1.0f;
-      for (int mt = 0; mt < MT; ++mt) aq[slot][mt] = 1.0f;
-      return;
-#endif
       const int k = ks * 2 + (lane >> 5);
       bq[slot][0] = Bs[buf][k][wn * 64 + (lane & 31)];
       bq[slot][1] = Bs[buf][k][wn * 64 + 32 + (lane & 31)];
@@ -233,12 +221,11 @@ __global__ __launch_bounds__(256, MT == 2 ? 4 : 2) void conv1d_mfma_f32_kernel(C
     }
     return;
   }
-#if !defined(QPG_CONV_PROBE) || QPG_CONV_PROBE < 4
   if (a.vec_out) {
     // A lane of the 32x32 accumulator tile holds ONE channel of 16 positions: written out as it lies, every store /
     // gate / residual access is 64 scattered dwords.  Each wave turns its tiles through 2 KB of the (now idle) operand
     // tiles instead - 16 positions x 32 channels per pass, written as the accumulators lie, read back as 16-byte rows -
-    // so that a wave instruction moves whole 128-byte lines, a quarter of the memory instructions.  (Probe 4 of
+    // so that a wave instruction moves whole 128-byte lines, a quarter of the memory instructions.  (Measured in
     // experiments/conv_probe: the scalar epilogue was 15 % of a k3 512 -> 512 layer at T = 120.)
     __syncthreads();                                   // the last slice's operand reads are done
     float* stage = w < 2 ? &As[0][0][0] + w * 512 : &Bs[0][0][0] + (w - 2) * 512;
@@ -286,7 +273,6 @@ __global__ __launch_bounds__(256, MT == 2 ? 4 : 2) void conv1d_mfma_f32_kernel(C
         }
     return;
   }
-#endif
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     const int n = n0 + wn * 64 + half * 32 + (lane & 31);
@@ -303,9 +289,6 @@ __global__ __launch_bounds__(256, MT == 2 ? 4 : 2) void conv1d_mfma_f32_kernel(C
         const int t = (int)(m - (int64_t)b * a.T_out);
         const int64_t o = ((int64_t)b * a.T_y + (int64_t)t * a.out_stride + a.out_offset) * a.Cout + n;
         float v = acc[mt][half][r] + bias;
-#if defined(QPG_CONV_PROBE) && QPG_CONV_PROBE == 4
-        if (v != 12345.678f) continue;        // probe: keep the MFMAs alive, skip the epilogue's memory traffic
-#endif
         if (a.relu_out) v = fmaxf(v, 0.f);
         if (a.gate) v = a.gate[o] > 0.f ? v : 0.f;
         if (a.res) v = a.res[o] + v;

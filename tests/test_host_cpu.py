@@ -80,6 +80,31 @@ def test_product_library_exports_no_debug_hooks_and_is_built_from_this_tree():
     assert lib.qpg_ctx_set_option(None, 0, 1) == -1 and "null context" in _lib.last_error()
 
 
+def test_kernel_sources_take_no_build_knobs():
+    """The product kernels are one program: no -D ablation, timer or A/B switch compiles parts of them in or out.  Every
+    #if / #ifdef / #ifndef / #elif of csrc/*.hip and csrc/*.h may test the macros listed here and nothing else (in
+    particular no `#ifndef X / #define X default` wrapper around a constant)."""
+    import re
+    from qpgesture_amd import build
+    allowed = {"QPG_DEBUG_HOOKS", "QPG_BUILD_ID", "QPG_CHECK_RCCL_ABI", "QPG_HAVE_RCCL_H", "__has_include", "__cplusplus"}
+    paths = [p for p in build.sources() + build.headers() if os.path.dirname(p) == build.CSRC]
+    assert len(paths) >= 17
+    directives, bad = 0, []
+    for path in paths:
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+                if not m:
+                    continue
+                directives += 1
+                cond = re.sub(r"//.*|/\*.*?\*/|<[^>]*>|\"[^\"]*\"", " ", m.group(2))
+                names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+                if names - allowed:
+                    bad.append("%s:%d: %s" % (os.path.basename(path), no, sorted(names - allowed)))
+    assert directives >= 5                      # (the hooks blocks, the build id, the RCCL header check: the scan sees them)
+    assert not bad, "conditional compilation on macros outside the allow-list:\n" + "\n".join(bad)
+
+
 def test_error_reporting_without_gpu():
     import torch
     if torch.cuda.is_available():
@@ -557,7 +582,9 @@ def test_audio_object_uses_m0_only_in_the_dma_asm():
                 movs += 1
             else:
                 uses_out.append(l)
-    assert movs >= 30 and not uses_out, uses_out[:5]
+    # the scan must see the DMA sites: an instantiation of audio_cosine_mx2_kernel issues the query tile at 4 places (the
+    # prologue and the 3 unrolled stages), 3 one-KB pieces each = 12 moves; the launches instantiate it twice (f32 / f16 base)
+    assert movs >= 2 * 12 and not uses_out, uses_out[:5]
 
 
 def test_sorted_rows_drop_later_duplicates_of_a_code():
