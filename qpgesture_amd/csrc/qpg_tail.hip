@@ -876,6 +876,26 @@ static bool tabulated_walk_ok(bool serial_walk, int steps, int K, int Qc, GateGe
          ((steps * 2 * K) % 8) == 0;
 }
 
+// A kernel gets 64 KiB of LDS, static and dynamic together, unless its launcher asks for more.  The product's K = 512 / 8
+// steps stays at half of that; the largest shapes the predicates above and below admit do not (K = 1024 / 8 steps: 64 KiB
+// of tables + gate_chase_kernel's 4 112 static bytes, or match_walk_kernel's 3 360; 16 steps x K = 768: 96 KiB + 3 360).
+// Those launches raise the kernel's limit first, like the selects (qpg_select.hip); one the device cannot grant comes
+// back as QPG_EHIP before anything has been launched.  (The walk's kernels hold less than 8 KiB of static LDS.)
+static int walk_lds_ok(const char* name, const void* kernel, size_t dyn) {
+  if (dyn <= 56 * 1024) return QPG_OK;
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) {
+    qpg_set_error("%s: cannot read the kernel's attributes", name);
+    return QPG_EHIP;
+  }
+  if (fa.sharedSizeBytes + dyn > 64 * 1024 &&
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+    qpg_set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", name, dyn);
+    return QPG_EHIP;
+  }
+  return QPG_OK;
+}
+
 static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
                             const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
                             const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx,
@@ -920,6 +940,15 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
   }
   QPG_REQUIRE(n_takes <= 0 || (takes_ws && takes_ws_bytes >= qpg_match_steps_takes_ws_bytes(n_takes, M, steps)),
               "qpg_match_steps_takes: workspace too small (qpg_match_steps_takes_ws_bytes)");
+  {
+    const size_t lds_chase = (size_t)2 * steps * 2 * K * sizeof(uint16_t);
+    int rc = QPG_OK;
+    if (!tabulated) rc = walk_lds_ok("match_walk_kernel", reinterpret_cast<const void*>(match_walk_kernel), lds);
+    else if (n_takes > 0)
+      rc = walk_lds_ok("gate_chase_takes_kernel", reinterpret_cast<const void*>(gate_chase_takes_kernel), lds_chase);
+    else rc = walk_lds_ok("gate_chase_kernel", reinterpret_cast<const void*>(gate_chase_kernel), lds_chase);
+    if (rc != QPG_OK) return rc;
+  }
   int32_t* T0 = gate_tables;
   int32_t* T1 = gate_tables + (int64_t)Q * K;
   if (prefused) {

@@ -98,15 +98,21 @@ def tables(D, cand_code, K, absent):
     return dist, idx, rank
 
 
+def fused_scores(pos_rank, freq_rank, rank_row):
+    """(pos_rank[p][c] + freq_rank[c] * 0.05) + rank_row[c] in f64, in that order of operations -> f64 [P][K]."""
+    fixed = np.asarray(pos_rank).astype(np.float64) + np.asarray(freq_rank).astype(np.float64)[None, :] * 0.05
+    return fixed + np.asarray(rank_row).astype(np.float64)[None, :]
+
+
 def fuse_best(pos_rank, freq_rank, rank, top_n=1):
     """The walk's rank fusion: per (query, previous code p) the top_n (1 or 2) codes with the smallest score
-    (pos_rank[p][c] + 0.05 freq_rank[c]) + rank[q][c] in f64, lowest code among equals.  -> int [Q][K][top_n]."""
-    fixed = pos_rank.astype(np.float64) + 0.05 * freq_rank.astype(np.float64)[None, :]
+    (pos_rank[p][c] + 0.05 freq_rank[c]) + rank[q][c] in f64, lowest code among equals.  -> int [Q][K][top_n].
+    A plain argmin over the values given: the rows of `rank` need not be permutations."""
     Q, K = rank.shape
-    out = np.empty((Q, K, top_n), np.int64)
-    rows = np.arange(K)
+    out = np.empty((Q, pos_rank.shape[0], top_n), np.int64)
+    rows = np.arange(pos_rank.shape[0])
     for q in range(Q):
-        s = fixed + rank[q].astype(np.float64)[None, :]
+        s = fused_scores(pos_rank, freq_rank, rank[q])
         for n in range(top_n):
             out[q, :, n] = s.argmin(axis=1)                    # (the first hit: the lowest code)
             s[rows, out[q, :, n]] = np.inf
