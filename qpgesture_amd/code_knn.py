@@ -1174,29 +1174,35 @@ class CodeKNN:
             return seed_phase.to(self.db.device, torch.float32).contiguous()
         return torch.as_tensor(np.asarray(seed_phase, np.float32), device=self.db.device).contiguous()
 
-    def _launch_walk(self, T, q0, Qt, rows, mode, prefusable, M, steps, seed, sp, outs, chains=None):
-        """The walk over table rows [q0, q0 + Qt): qpg_match_steps (chains None; seed: the seed code) or
-        qpg_match_steps_batch (`chains` independent clips back to back; seed: their i32 seed codes in device-readable
-        memory).  sp: the f32 [8][16] seed phase block(s); outs = (codes, phases, votes, status).  The tables' own gate
-        tables are taken as they are (QPG_MODE_PREFUSED) when they cover exactly these rows and `prefusable`; otherwise
-        the walk fuses the ranks itself into a scratch table of `rows` rows.  Returns the gate tables used."""
-        db, dev = self.db, self.db.device
+    def _walk_args(self, T, q0, Qt, rows, mode, prefusable):
+        """The arguments every walk over table rows [q0, q0 + Qt) starts with (the mode word, M, steps and K follow them),
+        the gate tables to use and the mode word.  The tables' own gate tables are taken as they are (QPG_MODE_PREFUSED)
+        when they cover exactly these rows and `prefusable`; otherwise the walk fuses the ranks itself into a scratch
+        table of `rows` rows."""
+        db = self.db
         gate = T.get("gate_tables")
         prefused = prefusable and gate is not None and mode == MODE_AUD_TXT and gate.shape[1] == Qt
         if not prefused:
-            gate = torch.empty((3, rows, db.K), dtype=torch.int32, device=dev)
-        mode_w = mode | (_lib.QPG_MODE_PREFUSED if prefused else 0)
-        if chains is None and self.serial_walk:
-            mode_w |= _lib.QPG_MODE_SERIAL_WALK
+            gate = torch.empty((3, rows, db.K), dtype=torch.int32, device=db.device)
         a_cidx, a_pslot, a_G = self._audio_grid()
         tabs = [None if T[k] is None else T[k][q0:q0 + Qt] for k in ("aud_rank", "aud_idx", "txt_rank", "txt_idx")]
         head = (*tabs, db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_pslot, a_G, db.txt_cidx,
-                db.txt_pslot, db.Gt, db.phase, db.Tp, mode_w, M, steps, db.K)
+                db.txt_pslot, db.Gt, db.phase, db.Tp)
+        return head, gate, mode | (_lib.QPG_MODE_PREFUSED if prefused else 0)
+
+    def _launch_walk(self, T, q0, Qt, rows, mode, prefusable, M, steps, seed, sp, outs, chains=None):
+        """The walk over table rows [q0, q0 + Qt): qpg_match_steps (chains None; seed: the seed code) or
+        qpg_match_steps_batch (`chains` independent clips back to back; seed: their i32 seed codes in device-readable
+        memory).  sp: the f32 [8][16] seed phase block(s); outs = (codes, phases, votes, status).  Returns _walk_args' gate."""
+        db, dev = self.db, self.db.device
+        head, gate, mode_w = self._walk_args(T, q0, Qt, rows, mode, prefusable)
+        if chains is None and self.serial_walk:
+            mode_w |= _lib.QPG_MODE_SERIAL_WALK
         guard = self._guard_stats[1:2]
         if chains is None:
-            _lib.call("qpg_match_steps", dev, *head, seed, sp, gate, *outs, guard)
+            _lib.call("qpg_match_steps", dev, *head, mode_w, M, steps, db.K, seed, sp, gate, *outs, guard)
         else:
-            _lib.call("qpg_match_steps_batch", dev, *head, chains, seed, sp, gate, *outs, 2, guard)
+            _lib.call("qpg_match_steps_batch", dev, *head, mode_w, M, steps, db.K, chains, seed, sp, gate, *outs, 2, guard)
         return gate
 
     def walk(self, T, n_windows, window_offset=0, mode=MODE_AUD_TXT, seed_code=None, seed_phase=None, sync=True,

@@ -6,7 +6,6 @@
 // the host.  Float paths reproduce the reference's arithmetic: combined scores in float64 in the
 // reference's operation order, the 128-d phase-gate cosine in scikit-learn's float32 order.
 #include "qpg_common.h"
-#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
 // pose-signature distance table: out[p][c] = |sig[p] - sig[c]|_2 (f32), +inf on the diagonal
@@ -44,19 +43,6 @@ __device__ __forceinline__ float lane4_sum(float v, int l) {
   const float pair = (l & 1) ? f_add(o1, v) : f_add(v, o1);  // lanes 0,1 -> l0+l1 ; lanes 2,3 -> l2+l3
   const float o2 = __shfl_xor(pair, 2, 64);
   return (l & 2) ? f_add(o2, pair) : f_add(pair, o2);         // (l0+l1)+(l2+l3)
-}
-
-__device__ __forceinline__ float einsum_sq_128(const float* v, int l) {
-  float a = 0.f;
-#pragma unroll
-  for (int g = 0; g < 8; ++g) {
-#pragma unroll
-    for (int u = 3; u >= 0; --u) {
-      const float x = v[g * 16 + u * 4 + l];
-      a = f_add(f_mul(x, x), a);
-    }
-  }
-  return lane4_sum(a, l);
 }
 
 struct ArgMin {
@@ -157,6 +143,70 @@ __global__ __launch_bounds__(256) void fuse_best_kernel(const int16_t* __restric
 // index among equal scores (a later rank r == best with a zero pose / frequency part can still tie: the scan continues
 // while r <= best).  Block = the 16 previous codes p0..p0+15 of one step q (K % 16 == 0).  A row that is not a permutation
 // (never produced by the rank kernels; checked anyway) makes its block scan every code.
+
+// the ArgMin of lane ^ PJ (the f64 value as two DPP moves)
+template <int PJ>
+__device__ __forceinline__ ArgMin argmin_xchg(ArgMin m) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(m.v);
+  const unsigned int lo = (unsigned int)lane_xor<PJ>((int)(unsigned int)b);
+  const unsigned int hi = (unsigned int)lane_xor<PJ>((int)(unsigned int)(b >> 32));
+  return ArgMin{__longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)), lane_xor<PJ>(m.i)};
+}
+
+// inv[t][r] = the code at rank r of rank row t (NR rows of K codes: rk0, rk1), by the whole block.  Returns whether some
+// row is not a permutation of 0..K-1 (`bad`: a block-shared word).
+template <int NR>
+__device__ __forceinline__ bool inverse_ranks(const int16_t* rk0, const int16_t* rk1, int K, int16_t* inv, int* bad) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *bad = 0;
+  for (int c = tid; c < NR * K; c += blockDim.x) inv[c] = -1;
+  __syncthreads();
+  for (int c = tid; c < K; c += blockDim.x) {
+    const int r0 = rk0[c], r1 = NR == 2 ? rk1[c] : 0;
+    if ((unsigned)r0 < (unsigned)K) inv[r0] = (int16_t)c; else *bad = 1;
+    if (NR == 2) {
+      if ((unsigned)r1 < (unsigned)K) inv[K + r1] = (int16_t)c; else *bad = 1;
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < NR * K; c += blockDim.x)
+    if (inv[c] < 0) *bad = 1;
+  __syncthreads();
+  return *bad != 0;
+}
+
+// The scan of one rank row by a 16-lane group (l16: the lane inside it): iv = the row's inverse, rk = the row, pr = the
+// previous code's pos_rank row.  Four chunks of 16 ranks per round, their gathers in flight together: a task needs ~3
+// chunks, and a round is one dependent gather latency either way.  `full`: every code, in code order.
+__device__ __forceinline__ ArgMin ranked_scan(const int16_t* iv, const int16_t* rk, const int16_t* pr,
+                                              const int16_t* freq_rank, int K, bool full, int l16) {
+  ArgMin m{__builtin_inf(), 0x7fffffff};
+  for (int base = 0; base < K; base += 64) {
+    if (!full && (double)base > m.v) break;                   // (m is uniform over the group after the reduction)
+    int c[4];
+    double pv[4], fv[4], rr[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int r = base + 16 * u + l16;
+      const bool ok = r < K;
+      c[u] = ok ? (full ? r : (int)iv[r]) : -1;
+      pv[u] = ok ? (double)pr[c[u]] : 0.0;
+      fv[u] = ok ? (double)freq_rank[c[u]] : 0.0;
+      rr[u] = ok ? (full ? (double)rk[c[u]] : (double)r) : 0.0;
+    }
+    ArgMin x{__builtin_inf(), 0x7fffffff};
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (c[u] >= 0) x = amin(x, ArgMin{(pv[u] + fv[u] * 0.05) + rr[u], c[u]});
+    x = amin(x, argmin_xchg<8>(x));
+    x = amin(x, argmin_xchg<4>(x));
+    x = amin(x, argmin_xchg<2>(x));
+    x = amin(x, argmin_xchg<1>(x));
+    m = amin(m, x);
+  }
+  return m;
+}
+
 __global__ __launch_bounds__(256) void fuse_best_ranked_kernel(const int16_t* __restrict__ rank0,
                                                                const int32_t* __restrict__ idx0,
                                                                const int16_t* __restrict__ rank1,
@@ -170,58 +220,12 @@ __global__ __launch_bounds__(256) void fuse_best_ranked_kernel(const int16_t* __
   const int64_t task = (int64_t)blockIdx.x * 16 + (tid >> 4);            // (q, p): one per 16-lane group
   const int q = (int)(((int64_t)blockIdx.x * 16) / K);
   const int p = (int)(task - (int64_t)q * K);
-  if (tid == 0) bad = 0;
-  for (int c = tid; c < 2 * K; c += blockDim.x) inv[c] = -1;
-  __syncthreads();
-  for (int c = tid; c < K; c += blockDim.x) {
-    const int ra = rank0[(int64_t)q * K + c], rt = rank1[(int64_t)q * K + c];
-    if ((unsigned)ra < (unsigned)K) inv[ra] = (int16_t)c; else bad = 1;
-    if ((unsigned)rt < (unsigned)K) inv[K + rt] = (int16_t)c; else bad = 1;
-  }
-  __syncthreads();
-  for (int c = tid; c < 2 * K; c += blockDim.x)
-    if (inv[c] < 0) bad = 1;
-  __syncthreads();
-  const bool full = bad != 0;
+  const int16_t* ra = rank0 + (int64_t)q * K;
+  const int16_t* rt = rank1 + (int64_t)q * K;
+  const bool full = inverse_ranks<2>(ra, rt, K, inv, &bad);
   const int16_t* pr = pos_rank + (int64_t)p * K;
-  auto xchg = [](ArgMin m, auto tag) {
-    constexpr int PJ = decltype(tag)::value;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(m.v);
-    const unsigned int lo = (unsigned int)lane_xor<PJ>((int)(unsigned int)b);
-    const unsigned int hi = (unsigned int)lane_xor<PJ>((int)(unsigned int)(b >> 32));
-    return ArgMin{__longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)), lane_xor<PJ>(m.i)};
-  };
-  // (four chunks of 16 ranks per round, their gathers in flight together: a task needs ~3 chunks, and a round is one
-  // dependent gather latency either way)
-  auto scan = [&](const int16_t* iv, const int16_t* rk) {
-    ArgMin m{__builtin_inf(), 0x7fffffff};
-    for (int base = 0; base < K; base += 64) {
-      if (!full && (double)base > m.v) break;                 // (m is uniform over the group after the reduction)
-      int c[4];
-      double pv[4], fv[4], rr[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int r = base + 16 * u + l16;
-        const bool ok = r < K;
-        c[u] = ok ? (full ? r : (int)iv[r]) : -1;
-        pv[u] = ok ? (double)pr[c[u]] : 0.0;
-        fv[u] = ok ? (double)freq_rank[c[u]] : 0.0;
-        rr[u] = ok ? (full ? (double)rk[c[u]] : (double)r) : 0.0;
-      }
-      ArgMin x{__builtin_inf(), 0x7fffffff};
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c[u] >= 0) x = amin(x, ArgMin{(pv[u] + fv[u] * 0.05) + rr[u], c[u]});
-      x = amin(x, xchg(x, std::integral_constant<int, 8>{}));
-      x = amin(x, xchg(x, std::integral_constant<int, 4>{}));
-      x = amin(x, xchg(x, std::integral_constant<int, 2>{}));
-      x = amin(x, xchg(x, std::integral_constant<int, 1>{}));
-      m = amin(m, x);
-    }
-    return m;
-  };
-  const ArgMin ma = scan(inv, rank0 + (int64_t)q * K);
-  const ArgMin mt = scan(inv + K, rank1 + (int64_t)q * K);
+  const ArgMin ma = ranked_scan(inv, ra, pr, freq_rank, K, full, l16);
+  const ArgMin mt = ranked_scan(inv + K, rt, pr, freq_rank, K, full, l16);
   if (l16 == 0) {
     T0[task] = idx0[(int64_t)q * K + ma.i];
     T1[task] = idx1[(int64_t)q * K + mt.i];
@@ -243,51 +247,9 @@ __global__ __launch_bounds__(256) void fuse_best_ranked_one_kernel(const int16_t
   const int64_t task = (int64_t)blockIdx.x * 16 + (tid >> 4);            // (q, p): one per 16-lane group
   const int q = (int)(((int64_t)blockIdx.x * 16) / K);
   const int p = (int)(task - (int64_t)q * K);
-  if (tid == 0) bad = 0;
-  for (int c = tid; c < K; c += blockDim.x) inv[c] = -1;
-  __syncthreads();
-  for (int c = tid; c < K; c += blockDim.x) {
-    const int r = rank[(int64_t)q * K + c];
-    if ((unsigned)r < (unsigned)K) inv[r] = (int16_t)c; else bad = 1;
-  }
-  __syncthreads();
-  for (int c = tid; c < K; c += blockDim.x)
-    if (inv[c] < 0) bad = 1;
-  __syncthreads();
-  const bool full = bad != 0;
-  const int16_t* pr = pos_rank + (int64_t)p * K;
   const int16_t* rk = rank + (int64_t)q * K;
-  auto xchg = [](ArgMin m, auto tag) {
-    constexpr int PJ = decltype(tag)::value;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(m.v);
-    const unsigned int lo = (unsigned int)lane_xor<PJ>((int)(unsigned int)b);
-    const unsigned int hi = (unsigned int)lane_xor<PJ>((int)(unsigned int)(b >> 32));
-    return ArgMin{__longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)), lane_xor<PJ>(m.i)};
-  };
-  ArgMin m{__builtin_inf(), 0x7fffffff};
-  for (int base = 0; base < K; base += 64) {
-    if (!full && (double)base > m.v) break;                   // (m is uniform over the group after the reduction)
-    int c[4];
-    double pv[4], fv[4], rr[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = base + 16 * u + l16;
-      const bool ok = r < K;
-      c[u] = ok ? (full ? r : (int)inv[r]) : -1;
-      pv[u] = ok ? (double)pr[c[u]] : 0.0;
-      fv[u] = ok ? (double)freq_rank[c[u]] : 0.0;
-      rr[u] = ok ? (full ? (double)rk[c[u]] : (double)r) : 0.0;
-    }
-    ArgMin x{__builtin_inf(), 0x7fffffff};
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (c[u] >= 0) x = amin(x, ArgMin{(pv[u] + fv[u] * 0.05) + rr[u], c[u]});
-    x = amin(x, xchg(x, std::integral_constant<int, 8>{}));
-    x = amin(x, xchg(x, std::integral_constant<int, 4>{}));
-    x = amin(x, xchg(x, std::integral_constant<int, 2>{}));
-    x = amin(x, xchg(x, std::integral_constant<int, 1>{}));
-    m = amin(m, x);
-  }
+  const bool full = inverse_ranks<1>(rk, nullptr, K, inv, &bad);
+  const ArgMin m = ranked_scan(inv, rk, pos_rank + (int64_t)p * K, freq_rank, K, full, l16);
   if (l16 == 0) T[task] = idx[(int64_t)q * K + m.i];
 }
 
@@ -318,6 +280,25 @@ struct TailArgs {
                              //     [1]: copy of *guard_flags (0 without it)
   const int32_t* guard_flags;  // the sweeps' / selects' trouble word (stats[1]), or NULL: rides out with the results
 };
+
+// The last stores of a walk, by the whole block.  The status pair is written LAST and behind a system-scope fence: when
+// the outputs live in pinned host memory (the matcher's zero-copy results) a host that sees the pair also sees the codes
+// and votes of every thread above.  `bad`: a register of thread 0 or a block-shared word, read behind the barrier.
+__device__ __forceinline__ void write_status_pair(const TailArgs& A, const int& bad) {
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    A.out_status[0] = bad;
+    __threadfence_system();
+    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
+  }
+}
+
+// The state a chain's first step starts from: its seed code -> *p, its seed phase block (128 floats) returned.
+__device__ __forceinline__ const float* chain_seed(const TailArgs& A, int chain, int* p) {
+  *p = A.seed_codes ? A.seed_codes[chain] : A.seed_code;
+  return A.seed_phase + (int64_t)chain * 128;
+}
 
 // ---------------------------------------------------------------------------------------------
 // The sequential walk: ONE wave.  A workgroup of one wave makes __syncthreads() a plain LDS fence, so the
@@ -380,7 +361,8 @@ __global__ __launch_bounds__(64) void match_walk_kernel(TailArgs A) {
 
   const int lane = threadIdx.x, K = A.K;
   // the running phase block (8 frames x [8 phase | 8 amp] = 128 floats) lives in registers: 2 floats per lane
-  float2 prev = reinterpret_cast<const float2*>(A.seed_phase)[lane];
+  int prev_code;
+  float2 prev = reinterpret_cast<const float2*>(chain_seed(A, 0, &prev_code))[lane];
   if (lane < A.G0) {
     s_cidx[lane] = A.cidx0[lane];
     s_pslot[lane] = A.pslot0[lane];
@@ -389,7 +371,6 @@ __global__ __launch_bounds__(64) void match_walk_kernel(TailArgs A) {
     s_cidx[64 + lane] = A.cidx1[lane];
     s_pslot[64 + lane] = A.pslot1[lane];
   }
-  int prev_code = A.seed_codes ? A.seed_codes[0] : A.seed_code;
   int bad = 0;
   const float eps10 = 10.f * 1.1920928955078125e-07f;
   const int last_idx = A.codes_per_window - 1;                 // the next window is seeded by this kept code
@@ -491,13 +472,7 @@ __global__ __launch_bounds__(64) void match_walk_kernel(TailArgs A) {
     if (lane < A.codes_per_window) A.out_codes[(int64_t)w * A.codes_per_window + lane] = wincodes[lane];
     prev_code = wincodes[last_idx];
   }
-  __threadfence_system();          // (status pair last, behind a system-scope fence: see gate_chase_kernel)
-  __syncthreads();
-  if (lane == 0) {
-    A.out_status[0] = bad;
-    __threadfence_system();
-    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
-  }
+  write_status_pair(A, bad);
 }
 
 
@@ -593,8 +568,7 @@ __global__ __launch_bounds__(256) void gate_table_kernel(TailArgs A, GateGeom ge
   int p;
   const float* prev;                                    // 128 floats: the previous phase block
   if (first) {
-    p = A.seed_codes ? A.seed_codes[chain] : A.seed_code;
-    prev = A.seed_phase + (int64_t)chain * 128;
+    prev = chain_seed(A, chain, &p);
   } else {
     const int pp = sigma >> 1, kp = sigma & 1;
     const int ci = (kp ? A.T1 : A.T0)[(int64_t)(q - 1) * K + pp];
@@ -624,8 +598,9 @@ __global__ __launch_bounds__(GD_THREADS) void gate_table_dedup_kernel(TailArgs A
   uint16_t* out = Gt + (int64_t)q * 2 * K;
   if (q == chain * Qc) {                        // a chain's first step: the seed's state only
     if (tid < 8) {
-      const int p = A.seed_codes ? A.seed_codes[chain] : A.seed_code;
-      const unsigned int g = gate_eval(A, q, p, A.seed_phase + (int64_t)chain * 128, lane);
+      int p;
+      const float* prev = chain_seed(A, chain, &p);
+      const unsigned int g = gate_eval(A, q, p, prev, lane);
       if (tid == 0) out[0] = (uint16_t)g;
     }
     return;
@@ -672,11 +647,60 @@ __global__ __launch_bounds__(GD_THREADS) void gate_table_dedup_kernel(TailArgs A
 }
 
 #define QPG_CHASE_QMAX 2048
+
+// The chase's window loop, by the whole block.  Two LDS buffers of per_w u16 (one window's gate table [steps][2K]): the
+// waves behind wave 0 stage window w + 1's table while chase(w, table of window w) runs on wave 0.
+template <class Chase>
+__device__ __forceinline__ void chase_windows(uint16_t* gl, const uint16_t* __restrict__ Gt, int M, int per_w, Chase chase) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  auto stage = [&](int w, int first, int step) {
+    const int4* src = reinterpret_cast<const int4*>(Gt + (int64_t)w * per_w);
+    int4* dst = reinterpret_cast<int4*>(gl + (size_t)(w & 1) * per_w);
+    for (int v = first; v < per_w / 8; v += step) dst[v] = src[v];
+  };
+  stage(0, tid, nt);
+  __syncthreads();
+  for (int w = 0; w < M; ++w) {
+    if (tid >= 64 && w + 1 < M) stage(w + 1, tid - 64, nt - 64);
+    chase(w, gl + (size_t)(w & 1) * per_w);
+    __syncthreads();
+  }
+}
+
+// The parallel epilogue of a chased chain, by the whole block: sig[q] = the state (p << 1) | vote of step q; A's tables
+// and outputs are the chain's own.  The winners' phase blocks, votes, codes; the absent-candidate check of every visited
+// gate (`bad`: block-shared, zeroed behind a barrier by the caller); the status pair last.
+__device__ __forceinline__ void walk_epilogue(const TailArgs& A, const uint16_t* sig, int* bad, int Q, int K) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int i = tid; i < Q * 32; i += nt) {                         // 32 x 16 B per phase block
+    const int q = i >> 5, v = i & 31;
+    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
+    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
+    int pb;
+    const float* blk = cand_block(A, fi, ci, &pb) + 384;
+    reinterpret_cast<f32x4*>(A.out_phase + (int64_t)q * 128)[v] = reinterpret_cast<const f32x4*>(blk)[v];
+    if (v == 0) {
+      A.out_vote[q] = fi;
+      if (A.T0[(int64_t)q * K + p] < 0 || A.T1[(int64_t)q * K + p] < 0) *bad = 1;
+    }
+  }
+  for (int i = tid; i < A.M * A.codes_per_window; i += nt) {
+    const int w = i / A.codes_per_window, c = i - w * A.codes_per_window;
+    const int q = w * A.steps + c / A.step_codes;
+    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
+    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
+    int pb;
+    cand_block(A, fi, ci, &pb);
+    A.out_codes[i] = A.code[pb + c % A.step_codes];
+  }
+  write_status_pair(A, *bad);
+}
+
 __global__ __launch_bounds__(1024) void gate_chase_kernel(TailArgs A, const uint16_t* __restrict__ Gt) {
   extern __shared__ __attribute__((aligned(16))) uint16_t gl[];     // 2 x [steps][2K]: current window + the next being staged
   __shared__ uint16_t sig[QPG_CHASE_QMAX];
   __shared__ int bad_s;
-  const int K = A.K, Q = A.M * A.steps, tid = threadIdx.x, nt = blockDim.x;
+  const int K = A.K, Q = A.M * A.steps, tid = threadIdx.x;
   const int per_w = A.steps * 2 * K;                                // u16 per window
   // one block per chain (clip): everything below is the chain's own slice of the tables and of the outputs
   const int chain = blockIdx.x;
@@ -690,56 +714,15 @@ __global__ __launch_bounds__(1024) void gate_chase_kernel(TailArgs A, const uint
   A.out_status += (int64_t)chain * A.status_stride;
   if (tid == 0) bad_s = 0;
   int sigma = 0;
-  // two LDS buffers: the other waves stage window w+1's table while lane 0 of wave 0 chases window w
-  auto stage = [&](int w, int first, int step) {
-    const int4* src = reinterpret_cast<const int4*>(Gt + (int64_t)w * per_w);
-    int4* dst = reinterpret_cast<int4*>(gl + (size_t)(w & 1) * per_w);
-    for (int v = first; v < per_w / 8; v += step) dst[v] = src[v];
-  };
-  stage(0, tid, nt);
-  __syncthreads();
-  for (int w = 0; w < A.M; ++w) {
-    if (tid >= 64 && w + 1 < A.M) stage(w + 1, tid - 64, nt - 64);
+  chase_windows(gl, Gt, A.M, per_w, [&](int w, const uint16_t* g) {
     if (tid == 0) {
-      const uint16_t* g = gl + (size_t)(w & 1) * per_w;
       for (int s = 0; s < A.steps; ++s) {
         sigma = (w == 0 && s == 0) ? g[0] : g[s * 2 * K + sigma];
         sig[w * A.steps + s] = (uint16_t)sigma;
       }
     }
-    __syncthreads();
-  }
-  // parallel epilogue: the winners' phase blocks, votes, codes; absent-candidate check of every visited gate
-  for (int i = tid; i < Q * 32; i += nt) {                         // 32 x 16 B per phase block
-    const int q = i >> 5, v = i & 31;
-    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
-    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
-    int pb;
-    const float* blk = cand_block(A, fi, ci, &pb) + 384;
-    reinterpret_cast<f32x4*>(A.out_phase + (int64_t)q * 128)[v] = reinterpret_cast<const f32x4*>(blk)[v];
-    if (v == 0) {
-      A.out_vote[q] = fi;
-      if (A.T0[(int64_t)q * K + p] < 0 || A.T1[(int64_t)q * K + p] < 0) bad_s = 1;
-    }
-  }
-  for (int i = tid; i < A.M * A.codes_per_window; i += nt) {
-    const int w = i / A.codes_per_window, c = i - w * A.codes_per_window;
-    const int q = w * A.steps + c / A.step_codes;
-    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
-    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
-    int pb;
-    cand_block(A, fi, ci, &pb);
-    A.out_codes[i] = A.code[pb + c % A.step_codes];
-  }
-  // The status pair is written LAST and behind a system-scope fence: when the outputs live in pinned host memory (the
-  // matcher's zero-copy results) a host that sees the pair also sees the codes and votes of every thread above.
-  __threadfence_system();
-  __syncthreads();
-  if (tid == 0) {
-    A.out_status[0] = bad_s;
-    __threadfence_system();
-    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
-  }
+  });
+  walk_epilogue(A, sig, &bad_s, Q, K);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -761,9 +744,10 @@ __global__ __launch_bounds__(256) void takes_step0_kernel(TailArgs A, int n_take
   const int task = (int)(((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3);
   const bool live = task < n_takes;
   const int take = live ? task : n_takes - 1;
-  int p = A.seed_codes[take];
+  int p;
+  const float* prev = chain_seed(A, take, &p);
   p = p < 0 ? 0 : (p >= A.K ? A.K - 1 : p);
-  const unsigned int g = gate_eval(A, 0, p, A.seed_phase + (int64_t)take * 128, lane);
+  const unsigned int g = gate_eval(A, 0, p, prev, lane);
   if (live && (lane & 7) == 0) step0[take] = (uint16_t)g;
 }
 
@@ -775,29 +759,19 @@ __global__ __launch_bounds__(1024) void gate_chase_takes_kernel(int M, int steps
                                                                 const uint16_t* __restrict__ step0,
                                                                 uint16_t* __restrict__ trail) {
   extern __shared__ __attribute__((aligned(16))) uint16_t gl[];     // 2 x [steps][2K]
-  const int tid = threadIdx.x, nt = blockDim.x;
+  const int tid = threadIdx.x;
   const int per_w = steps * 2 * K;                                  // u16 per window
   const int take = blockIdx.x * QPG_TAKES_PER_BLOCK + tid;
   const bool chaser = tid < QPG_TAKES_PER_BLOCK && take < n_takes;
-  auto stage = [&](int w, int first, int step) {
-    const int4* src = reinterpret_cast<const int4*>(Gt + (int64_t)w * per_w);
-    int4* dst = reinterpret_cast<int4*>(gl + (size_t)(w & 1) * per_w);
-    for (int v = first; v < per_w / 8; v += step) dst[v] = src[v];
-  };
-  stage(0, tid, nt);
-  __syncthreads();
   int sigma = chaser ? step0[take] : 0;
-  for (int w = 0; w < M; ++w) {
-    if (tid >= 64 && w + 1 < M) stage(w + 1, tid - 64, nt - 64);
+  chase_windows(gl, Gt, M, per_w, [&](int w, const uint16_t* g) {
     if (chaser) {
-      const uint16_t* g = gl + (size_t)(w & 1) * per_w;
       for (int s = 0; s < steps; ++s) {
         if (w | s) sigma = g[s * 2 * K + sigma];                    // (a table entry is (p << 1) | vote < 2K)
         trail[(int64_t)(w * steps + s) * n_takes + take] = (uint16_t)sigma;
       }
     }
-    __syncthreads();
-  }
+  });
 }
 
 // gate_chase_kernel's parallel epilogue, one block per take: the winners' phase blocks, votes, codes, the absent-candidate
@@ -814,34 +788,7 @@ __global__ __launch_bounds__(256) void takes_epilogue_kernel(TailArgs A, int n_t
   if (tid == 0) bad_s = 0;
   for (int q = tid; q < Q; q += nt) sig[q] = trail[(int64_t)q * n_takes + take];
   __syncthreads();
-  for (int i = tid; i < Q * 32; i += nt) {                         // 32 x 16 B per phase block
-    const int q = i >> 5, v = i & 31;
-    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
-    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
-    int pb;
-    const float* blk = cand_block(A, fi, ci, &pb) + 384;
-    reinterpret_cast<f32x4*>(A.out_phase + (int64_t)q * 128)[v] = reinterpret_cast<const f32x4*>(blk)[v];
-    if (v == 0) {
-      A.out_vote[q] = fi;
-      if (A.T0[(int64_t)q * K + p] < 0 || A.T1[(int64_t)q * K + p] < 0) bad_s = 1;
-    }
-  }
-  for (int i = tid; i < A.M * A.codes_per_window; i += nt) {
-    const int w = i / A.codes_per_window, c = i - w * A.codes_per_window;
-    const int q = w * A.steps + c / A.step_codes;
-    const int sg = sig[q], p = sg >> 1, fi = sg & 1;
-    const int ci = (fi ? A.T1 : A.T0)[(int64_t)q * K + p];
-    int pb;
-    cand_block(A, fi, ci, &pb);
-    A.out_codes[i] = A.code[pb + c % A.step_codes];
-  }
-  __threadfence_system();
-  __syncthreads();
-  if (tid == 0) {
-    A.out_status[0] = bad_s;
-    __threadfence_system();
-    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
-  }
+  walk_epilogue(A, sig, &bad_s, Q, K);
 }
 
 __global__ void status_only_kernel(int32_t* out_status, const int32_t* guard_flags) {
@@ -863,17 +810,27 @@ extern "C" int qpg_fuse_best_ranked(qpg_ctx* ctx, void* stream, const int16_t* r
   return QPG_OK;
 }
 
-// From how many chains per launch the gate table is deduplicated by the previous winner (gate_table_dedup_kernel; 0 =
-// never): the context's QPG_OPT_GATE_DEDUP_FROM_CHAINS (default 1; the tests set 0 to walk on round 4's plain table).
+// The walk's geometry, computed once per call.  The tabulated walk applies when the code that seeds the next window comes
+// from the window's LAST step (always true for the reference's grids: 8 steps x 4 codes, 30 kept) and the state fits 16
+// bits; the one-wave sequential walk otherwise.
+struct WalkGeom {
+  int codes_per_window;   // codes a window keeps of its steps * 4
+  GateGeom gate;
+  size_t lds_cand;        // match_walk_kernel: a window's two candidate tables, i32 [2][steps][K]
+  size_t lds_chase;       // the chase kernels: two windows' gate tables (double buffer), u16 2 x [steps][2K]
+  bool tabulated;
+};
 
-// The tabulated walk applies when the code that seeds the next window comes from the window's LAST step (always true for
-// the reference's grids: 8 steps x 4 codes, 30 kept) and the state fits 16 bits; the one-wave sequential walk otherwise.
-static bool tabulated_walk_ok(bool serial_walk, int steps, int K, int Qc, GateGeom* geo) {
-  const int codes_per_window = (steps * 4 < 30) ? steps * 4 : 30, last_idx = codes_per_window - 1;
-  *geo = GateGeom{last_idx / 4, last_idx % 4};
-  const size_t lds_g = (size_t)2 * steps * 2 * K * sizeof(uint16_t);     // two window tables (double buffer)
-  return !serial_walk && geo->s_last == steps - 1 && 2 * K <= 65536 && Qc <= QPG_CHASE_QMAX && lds_g <= 64 * 1024 &&
-         ((steps * 2 * K) % 8) == 0;
+static WalkGeom walk_geom(bool serial_walk, int steps, int K, int Qc) {
+  WalkGeom g;
+  g.codes_per_window = (steps * 4 < 30) ? steps * 4 : 30;
+  const int last_idx = g.codes_per_window - 1;
+  g.gate = GateGeom{last_idx / 4, last_idx % 4};
+  g.lds_cand = (size_t)2 * steps * K * sizeof(int32_t);
+  g.lds_chase = (size_t)2 * steps * 2 * K * sizeof(uint16_t);
+  g.tabulated = !serial_walk && g.gate.s_last == steps - 1 && 2 * K <= 65536 && Qc <= QPG_CHASE_QMAX &&
+                g.lds_chase <= 64 * 1024 && ((steps * 2 * K) % 8) == 0;
+  return g;
 }
 
 // A kernel gets 64 KiB of LDS, static and dynamic together, unless its launcher asks for more.  The product's K = 512 / 8
@@ -896,104 +853,117 @@ static int walk_lds_ok(const char* name, const void* kernel, size_t dyn) {
   return QPG_OK;
 }
 
-static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
-                            const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
-                            const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx,
-                            const int32_t* aud_pslot, int Ga, const int32_t* txt_cidx, const int32_t* txt_pslot,
-                            int Gt, const float* phase, int Tp, int mode, int M, int steps, int K, int seed_code,
-                            const float* seed_phase, int32_t* gate_tables, int32_t* out_codes, float* out_phase,
-                            int32_t* out_vote, int32_t* out_status, const int32_t* guard_flags, int n_chains,
-                            const int32_t* seed_codes, int64_t status_stride, int n_takes = 0,
-                            void* takes_ws = nullptr, size_t takes_ws_bytes = 0) {
-  QPG_REQUIRE(ctx && pos_rank && freq_rank && code && phase && seed_phase && gate_tables && out_codes && out_phase &&
-                  out_vote && out_status,
+// What qpg_match_steps, _batch and _takes pass on: first the arguments the three share, in the order of their parameter
+// lists (include/qpg.h describes them), then what only some of them have.
+struct WalkArgs {
+  const int16_t* aud_rank; const int32_t* aud_idx; const int16_t* txt_rank; const int32_t* txt_idx;
+  const int16_t* pos_rank; const int16_t* freq_rank; const int32_t* code; int code_ld;
+  const int32_t* aud_cidx; const int32_t* aud_pslot; int Ga;
+  const int32_t* txt_cidx; const int32_t* txt_pslot; int Gt;
+  const float* phase; int Tp, mode, M, steps, K;
+  const float* seed_phase; int32_t* gate_tables; int32_t* out_codes; float* out_phase; int32_t* out_vote;
+  int32_t* out_status; const int32_t* guard_flags;
+  int seed_code = 0;                     // qpg_match_steps: the one chain's seed
+  const int32_t* seed_codes = nullptr;   // _batch, _takes: [n_chains] / [n_takes] on the device
+  int n_chains = 1;                      // _batch
+  int64_t status_stride = 2;             // _batch, _takes
+  int n_takes = 0;                       // _takes, with its workspace
+  void* takes_ws = nullptr;
+  size_t takes_ws_bytes = 0;
+};
+
+// (QPG_OPT_GATE_DEDUP_FROM_CHAINS: from how many chains per launch the gate table is deduplicated by the previous winner,
+// gate_table_dedup_kernel; 0 = never, default 1 - the tests set 0 to walk on round 4's plain table.)
+static int match_steps_impl(qpg_ctx* ctx, void* stream, const WalkArgs& a) {
+  const int M = a.M, steps = a.steps, K = a.K, n_chains = a.n_chains, n_takes = a.n_takes;
+  QPG_REQUIRE(ctx && a.pos_rank && a.freq_rank && a.code && a.phase && a.seed_phase && a.gate_tables && a.out_codes &&
+                  a.out_phase && a.out_vote && a.out_status,
               "qpg_match_steps: null pointer");
-  QPG_REQUIRE(n_chains >= 1 && (n_chains == 1 || (seed_codes && status_stride >= 2)),
+  QPG_REQUIRE(n_chains >= 1 && (n_chains == 1 || (a.seed_codes && a.status_stride >= 2)),
               "qpg_match_steps_batch: n_chains >= 1, device seed codes and a status stride >= 2");
-  const bool serial_walk = (mode & QPG_MODE_SERIAL_WALK) != 0;
-  const bool prefused = (mode & QPG_MODE_PREFUSED) != 0;     // T0 | T1 of gate_tables were filled by qpg_fuse_best_ranked
-  mode &= ~(QPG_MODE_SERIAL_WALK | QPG_MODE_PREFUSED);
+  const bool serial_walk = (a.mode & QPG_MODE_SERIAL_WALK) != 0;
+  const bool prefused = (a.mode & QPG_MODE_PREFUSED) != 0;   // T0 | T1 of gate_tables were filled by qpg_fuse_best_ranked
+  const int mode = a.mode & ~(QPG_MODE_SERIAL_WALK | QPG_MODE_PREFUSED);
   QPG_REQUIRE(!prefused || mode == 0, "qpg_match_steps: QPG_MODE_PREFUSED goes with the two-modality mode");
   QPG_REQUIRE(mode >= 0 && mode <= 2, "qpg_match_steps: bad mode %d", mode);
-  QPG_REQUIRE(mode == QPG_MODE_TXT || (aud_rank && aud_idx && aud_cidx && aud_pslot && Ga > 0),
+  QPG_REQUIRE(mode == QPG_MODE_TXT || (a.aud_rank && a.aud_idx && a.aud_cidx && a.aud_pslot && a.Ga > 0),
               "qpg_match_steps: audio tables missing");
-  QPG_REQUIRE(mode == QPG_MODE_AUD || (txt_rank && txt_idx && txt_cidx && txt_pslot && Gt > 0),
+  QPG_REQUIRE(mode == QPG_MODE_AUD || (a.txt_rank && a.txt_idx && a.txt_cidx && a.txt_pslot && a.Gt > 0),
               "qpg_match_steps: text tables missing");
   QPG_REQUIRE(M >= 0 && steps > 0 && steps * 4 <= 64 && K > 0 && K <= 64 * QPG_KMAX_PER_LANE && (K % 4) == 0 &&
-                  seed_code >= 0 && seed_code < K && Ga <= 64 && Gt <= 64,
+                  a.seed_code >= 0 && a.seed_code < K && a.Ga <= 64 && a.Gt <= 64,
               "qpg_match_steps: bad size");
-  const size_t lds = (size_t)2 * steps * K * sizeof(int32_t);
-  QPG_REQUIRE(lds <= 96 * 1024, "qpg_match_steps: steps*K too large for the LDS gate tables");
+  const int Qc = M * steps;                  // steps of one chain
+  const int Q = Qc * n_chains;
+  const WalkGeom geo = walk_geom(serial_walk, steps, K, Qc);
+  QPG_REQUIRE(geo.lds_cand <= 96 * 1024, "qpg_match_steps: steps*K too large for the LDS gate tables");
   if (M == 0) {              // an empty clip still gets a defined status word (the host reads it with the results)
-    hipLaunchKernelGGL(status_only_kernel, dim3(1), dim3(1), 0, qpg_stream(stream), out_status, guard_flags);
+    hipLaunchKernelGGL(status_only_kernel, dim3(1), dim3(1), 0, qpg_stream(stream), a.out_status, a.guard_flags);
     QPG_LAUNCH_CHECK("status_only_kernel");
     return QPG_OK;
   }
-  const int Qc = M * steps;                  // steps of one chain
-  const int Q = Qc * n_chains;
-  GateGeom geo;
-  const bool tabulated = tabulated_walk_ok(serial_walk, steps, K, Qc, &geo);
-  if (n_takes > 0 && !tabulated) {           // (before anything is launched: the caller walks the takes one by one)
+  if (n_takes > 0 && !geo.tabulated) {       // (before anything is launched: the caller walks the takes one by one)
     qpg_set_error("qpg_match_steps_takes: the tabulated walk does not apply (serial walk asked for, or steps = %d / K = %d "
                   "/ %d steps per clip outside its geometry)", steps, K, Qc);
     return QPG_EUNSUP;
   }
-  QPG_REQUIRE(n_takes <= 0 || (takes_ws && takes_ws_bytes >= qpg_match_steps_takes_ws_bytes(n_takes, M, steps)),
+  QPG_REQUIRE(n_takes <= 0 || (a.takes_ws && a.takes_ws_bytes >= qpg_match_steps_takes_ws_bytes(n_takes, M, steps)),
               "qpg_match_steps_takes: workspace too small (qpg_match_steps_takes_ws_bytes)");
   {
-    const size_t lds_chase = (size_t)2 * steps * 2 * K * sizeof(uint16_t);
     int rc = QPG_OK;
-    if (!tabulated) rc = walk_lds_ok("match_walk_kernel", reinterpret_cast<const void*>(match_walk_kernel), lds);
+    if (!geo.tabulated) rc = walk_lds_ok("match_walk_kernel", reinterpret_cast<const void*>(match_walk_kernel), geo.lds_cand);
     else if (n_takes > 0)
-      rc = walk_lds_ok("gate_chase_takes_kernel", reinterpret_cast<const void*>(gate_chase_takes_kernel), lds_chase);
-    else rc = walk_lds_ok("gate_chase_kernel", reinterpret_cast<const void*>(gate_chase_kernel), lds_chase);
+      rc = walk_lds_ok("gate_chase_takes_kernel", reinterpret_cast<const void*>(gate_chase_takes_kernel), geo.lds_chase);
+    else rc = walk_lds_ok("gate_chase_kernel", reinterpret_cast<const void*>(gate_chase_kernel), geo.lds_chase);
     if (rc != QPG_OK) return rc;
   }
-  int32_t* T0 = gate_tables;
-  int32_t* T1 = gate_tables + (int64_t)Q * K;
+  int32_t* T0 = a.gate_tables;
+  int32_t* T1 = a.gate_tables + (int64_t)Q * K;
   if (prefused) {
     // (nothing: both tables are there)
   } else if (mode == 0 && (K % 16) == 0 && K <= 4096) {
     hipLaunchKernelGGL(fuse_best_ranked_kernel, dim3((unsigned)(((int64_t)Q * K) / 16)), dim3(256), 4 * (size_t)K,
-                       qpg_stream(stream), aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, Q, K, T0, T1);
+                       qpg_stream(stream), a.aud_rank, a.aud_idx, a.txt_rank, a.txt_idx, a.pos_rank, a.freq_rank, Q, K, T0,
+                       T1);
+    QPG_LAUNCH_CHECK("fuse_best_ranked_kernel");
   } else {
     dim3 grid((unsigned)(((int64_t)Q * K + 3) / 4), 1);
-    hipLaunchKernelGGL(fuse_best_kernel, grid, dim3(256), 0, qpg_stream(stream), aud_rank, aud_idx, txt_rank, txt_idx,
-                       pos_rank, freq_rank, Q, K, mode, T0, T1);
+    hipLaunchKernelGGL(fuse_best_kernel, grid, dim3(256), 0, qpg_stream(stream), a.aud_rank, a.aud_idx, a.txt_rank,
+                       a.txt_idx, a.pos_rank, a.freq_rank, Q, K, mode, T0, T1);
+    QPG_LAUNCH_CHECK("fuse_best_kernel");
   }
-  QPG_LAUNCH_CHECK("fuse_best_kernel");
   TailArgs A;
-  A.T0 = T0; A.T1 = T1; A.code = code; A.code_ld = code_ld;
+  A.T0 = T0; A.T1 = T1; A.code = a.code; A.code_ld = a.code_ld;
   const bool txt0 = (mode == QPG_MODE_TXT), txt1 = (mode != QPG_MODE_AUD);
-  A.cidx0 = txt0 ? txt_cidx : aud_cidx; A.pslot0 = txt0 ? txt_pslot : aud_pslot; A.G0 = txt0 ? Gt : Ga;
-  A.cidx1 = txt1 ? txt_cidx : aud_cidx; A.pslot1 = txt1 ? txt_pslot : aud_pslot; A.G1 = txt1 ? Gt : Ga;
-  A.phase = phase; A.Tp = Tp; A.M = M; A.steps = steps; A.step_codes = 4;
-  A.codes_per_window = (steps * 4 < 30) ? steps * 4 : 30;
-  A.K = K; A.seed_code = seed_code; A.seed_phase = seed_phase; A.seed_codes = seed_codes; A.n_chains = n_chains;
-  A.status_stride = status_stride;
-  A.out_codes = out_codes; A.out_phase = out_phase; A.out_vote = out_vote; A.out_status = out_status;
-  A.guard_flags = guard_flags;
-  const size_t lds_g = (size_t)2 * steps * 2 * K * sizeof(uint16_t);     // two window tables (double buffer)
-  if (!tabulated) {
+  A.cidx0 = txt0 ? a.txt_cidx : a.aud_cidx; A.pslot0 = txt0 ? a.txt_pslot : a.aud_pslot; A.G0 = txt0 ? a.Gt : a.Ga;
+  A.cidx1 = txt1 ? a.txt_cidx : a.aud_cidx; A.pslot1 = txt1 ? a.txt_pslot : a.aud_pslot; A.G1 = txt1 ? a.Gt : a.Ga;
+  A.phase = a.phase; A.Tp = a.Tp; A.M = M; A.steps = steps; A.step_codes = 4;
+  A.codes_per_window = geo.codes_per_window;
+  A.K = K; A.seed_code = a.seed_code; A.seed_phase = a.seed_phase; A.seed_codes = a.seed_codes; A.n_chains = n_chains;
+  A.status_stride = a.status_stride;
+  A.out_codes = a.out_codes; A.out_phase = a.out_phase; A.out_vote = a.out_vote; A.out_status = a.out_status;
+  A.guard_flags = a.guard_flags;
+  if (!geo.tabulated) {
     QPG_REQUIRE(n_chains == 1, "qpg_match_steps_batch: the sequential walk takes one chain per call");
-    hipLaunchKernelGGL(match_walk_kernel, dim3(1), dim3(64), lds, qpg_stream(stream), A);
+    hipLaunchKernelGGL(match_walk_kernel, dim3(1), dim3(64), geo.lds_cand, qpg_stream(stream), A);
     QPG_LAUNCH_CHECK("match_walk_kernel");
     return QPG_OK;
   }
-  uint16_t* gtab = reinterpret_cast<uint16_t*>(gate_tables + (int64_t)2 * Q * K);     // third [Q][K] i32 region
+  uint16_t* gtab = reinterpret_cast<uint16_t*>(a.gate_tables + (int64_t)2 * Q * K);   // third [Q][K] i32 region
   const int64_t lanes = (int64_t)Q * 2 * K * 8;
   const int dedup_from = ctx->opt[QPG_OPT_GATE_DEDUP_FROM_CHAINS];      // (qpg_ctx_set_option; 0: never)
   if (dedup_from > 0 && n_chains >= dedup_from && K <= 512) {
-    hipLaunchKernelGGL(gate_table_dedup_kernel, dim3((unsigned)Q), dim3(GD_THREADS), 0, qpg_stream(stream), A, geo, gtab);
+    hipLaunchKernelGGL(gate_table_dedup_kernel, dim3((unsigned)Q), dim3(GD_THREADS), 0, qpg_stream(stream), A, geo.gate,
+                       gtab);
     QPG_LAUNCH_CHECK("gate_table_dedup_kernel");
   } else {
     hipLaunchKernelGGL(gate_table_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, qpg_stream(stream), A,
-                       geo, gtab);
+                       geo.gate, gtab);
     QPG_LAUNCH_CHECK("gate_table_kernel");
   }
   if (n_takes > 0) {
     // the gate table above is the clip's (its row 0 holds take 0's step); every take's step 0, chase and epilogue
-    uint16_t* step0 = reinterpret_cast<uint16_t*>(takes_ws);
+    uint16_t* step0 = reinterpret_cast<uint16_t*>(a.takes_ws);
     uint16_t* trail = step0 + takes_trail_off(n_takes);
     const int stages = ctx->opt[QPG_OPT_TAKES_STAGES];                  // (7 unless a measurement asked for less)
     if (stages & 1) {
@@ -1003,8 +973,9 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
     }
     if (stages & 2) {
       hipLaunchKernelGGL(gate_chase_takes_kernel,
-                         dim3((unsigned)((n_takes + QPG_TAKES_PER_BLOCK - 1) / QPG_TAKES_PER_BLOCK)), dim3(1024), lds_g,
-                         qpg_stream(stream), M, steps, K, n_takes, (const uint16_t*)gtab, (const uint16_t*)step0, trail);
+                         dim3((unsigned)((n_takes + QPG_TAKES_PER_BLOCK - 1) / QPG_TAKES_PER_BLOCK)), dim3(1024),
+                         geo.lds_chase, qpg_stream(stream), M, steps, K, n_takes, (const uint16_t*)gtab,
+                         (const uint16_t*)step0, trail);
       QPG_LAUNCH_CHECK("gate_chase_takes_kernel");
     }
     if (stages & 4) {
@@ -1014,7 +985,8 @@ static int match_steps_impl(qpg_ctx* ctx, void* stream, const int16_t* aud_rank,
     }
     return QPG_OK;
   }
-  hipLaunchKernelGGL(gate_chase_kernel, dim3(n_chains), dim3(1024), lds_g, qpg_stream(stream), A, (const uint16_t*)gtab);
+  hipLaunchKernelGGL(gate_chase_kernel, dim3(n_chains), dim3(1024), geo.lds_chase, qpg_stream(stream), A,
+                     (const uint16_t*)gtab);
   QPG_LAUNCH_CHECK("gate_chase_kernel");
   return QPG_OK;
 }
@@ -1026,9 +998,11 @@ extern "C" int qpg_match_steps(qpg_ctx* ctx, void* stream, const int16_t* aud_ra
                                int Gt, const float* phase, int Tp, int mode, int M, int steps, int K, int seed_code,
                                const float* seed_phase, int32_t* gate_tables, int32_t* out_codes, float* out_phase,
                                int32_t* out_vote, int32_t* out_status, const int32_t* guard_flags) {
-  return match_steps_impl(ctx, stream, aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx,
-                          aud_pslot, Ga, txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, seed_code, seed_phase,
-                          gate_tables, out_codes, out_phase, out_vote, out_status, guard_flags, 1, nullptr, 2);
+  WalkArgs a{aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx, aud_pslot, Ga,
+             txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, seed_phase, gate_tables, out_codes, out_phase,
+             out_vote, out_status, guard_flags};
+  a.seed_code = seed_code;
+  return match_steps_impl(ctx, stream, a);
 }
 
 // Several INDEPENDENT clips (chains) of M windows each in one set of launches: the tables hold the chains' steps back to
@@ -1044,9 +1018,11 @@ extern "C" int qpg_match_steps_batch(qpg_ctx* ctx, void* stream, const int16_t* 
                                      int32_t* gate_tables, int32_t* out_codes, float* out_phase, int32_t* out_vote,
                                      int32_t* out_status, int64_t status_stride, const int32_t* guard_flags) {
   QPG_REQUIRE(M > 0 && seed_codes, "qpg_match_steps_batch: M > 0 and device seed codes");
-  return match_steps_impl(ctx, stream, aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx,
-                          aud_pslot, Ga, txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, 0, seed_phase, gate_tables,
-                          out_codes, out_phase, out_vote, out_status, guard_flags, n_chains, seed_codes, status_stride);
+  WalkArgs a{aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx, aud_pslot, Ga,
+             txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, seed_phase, gate_tables, out_codes, out_phase,
+             out_vote, out_status, guard_flags};
+  a.seed_codes = seed_codes; a.n_chains = n_chains; a.status_stride = status_stride;
+  return match_steps_impl(ctx, stream, a);
 }
 
 // n_takes takes of ONE clip (tables of Q = M x steps rows) in one set of launches: rank fusion (unless prefused) and the
@@ -1069,8 +1045,10 @@ extern "C" int qpg_match_steps_takes(qpg_ctx* ctx, void* stream, const int16_t* 
                                      void* workspace, size_t workspace_bytes) {
   QPG_REQUIRE(M > 0 && seed_codes && n_takes >= 1 && n_takes <= QPG_TAKES_MAX && status_stride >= 2,
               "qpg_match_steps_takes: M > 0, 1 <= n_takes <= %d, device seed codes and a status stride >= 2", QPG_TAKES_MAX);
-  return match_steps_impl(ctx, stream, aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx,
-                          aud_pslot, Ga, txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, 0, seed_phase, gate_tables,
-                          out_codes, out_phase, out_vote, out_status, guard_flags, 1, seed_codes, status_stride, n_takes,
-                          workspace, workspace_bytes);
+  WalkArgs a{aud_rank, aud_idx, txt_rank, txt_idx, pos_rank, freq_rank, code, code_ld, aud_cidx, aud_pslot, Ga,
+             txt_cidx, txt_pslot, Gt, phase, Tp, mode, M, steps, K, seed_phase, gate_tables, out_codes, out_phase,
+             out_vote, out_status, guard_flags};
+  a.seed_codes = seed_codes; a.status_stride = status_stride;
+  a.n_takes = n_takes; a.takes_ws = workspace; a.takes_ws_bytes = workspace_bytes;
+  return match_steps_impl(ctx, stream, a);
 }

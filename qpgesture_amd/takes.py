@@ -98,7 +98,7 @@ def walk_takes(knn, T, n_windows, seed_codes, seed_phases, mode, window_offset=0
     """CodeKNN.walk_takes (its docstring has the interface)."""
     import torch
     from . import _lib
-    from .code_knn import MODE_AUD_TXT, plan_takes
+    from .code_knn import plan_takes
     db, dev = knn.db, knn.db.device
     M, steps = int(n_windows), knn.n_steps()
     if seed_ptrs is None:
@@ -132,19 +132,12 @@ def walk_takes(knn, T, n_windows, seed_codes, seed_phases, mode, window_offset=0
             ov = ints_d[S * n_c:S * (n_c + n_v)].view(S, M, steps)
             st = ints_d[S * (n_c + n_v):].view(S, 2)
         q0, Q = int(window_offset) * steps, M * steps
-        gate = T.get("gate_tables")
-        prefused = gate is not None and mode == MODE_AUD_TXT and gate.shape[1] == Q and q0 == 0
-        if not prefused:
-            gate = torch.empty((3, Q, db.K), dtype=torch.int32, device=dev)
-        a_cidx, a_pslot, a_G = knn._audio_grid()
-        tabs = [None if T[k] is None else T[k][q0:q0 + Q] for k in ("aud_rank", "aud_idx", "txt_rank", "txt_idx")]
+        head, gate, mode_w = knn._walk_args(T, q0, Q, Q, mode, q0 == 0)
         nb = int(_lib.load().qpg_match_steps_takes_ws_bytes(S, M, steps))
         ws = knn._takes_ws = _grown_ws(knn._takes_ws, nb, dev)
         try:
-            _lib.call("qpg_match_steps_takes", dev, *tabs, db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx,
-                      a_pslot, a_G, db.txt_cidx, db.txt_pslot, db.Gt, db.phase, db.Tp,
-                      mode | (_lib.QPG_MODE_PREFUSED if prefused else 0), M, steps, db.K, S, sc_d, sp_d, gate, oc,
-                      out_phase, ov, st, 2, knn._guard_stats[1:2], ws, ws.numel())
+            _lib.call("qpg_match_steps_takes", dev, *head, mode_w, M, steps, db.K, S, sc_d, sp_d, gate, oc, out_phase, ov,
+                      st, 2, knn._guard_stats[1:2], ws, ws.numel())
         except _lib.Unsupported:
             # (the library refuses a geometry the plan let through: nothing was launched; the takes one at a time)
             if seed_ptrs is not None:

@@ -189,6 +189,13 @@ def main(out_path):
                                                     phases))
         print("%-44s %4d entries" % (name, len(cells[name])), flush=True)
 
+    # several takes of one clip: on the tables' own (prefused) gate tables, and fusing the ranks itself
+    seeds, phases = rng.randint(0, 512, size=5), rng.standard_normal((5, 8, 16)).astype(np.float32)
+    for name, for_walk in (("walk_takes/prefused", True), ("walk_takes/own_fusion", False)):
+        knn = matcher()
+        cells[name] = traced(lambda: knn.walk_takes(knn.sweep_tables(te_i, te_c, M, for_walk=for_walk), M, seeds, phases))
+        print("%-44s %4d entries" % (name, len(cells[name])), flush=True)
+
     sc, sp = matcher().init_code_phase()
     from qpgesture_amd.vqvae import VQVAE
     enc = VQVAE(None, 135, device=dev).load_state_dict(synth.make_vqvae_state_dict(7))
