@@ -58,6 +58,11 @@ int qpg_ctx_destroy(qpg_ctx* ctx);
  *                                   (tools/bench_takes.py times each kernel between two HIP events): a stage that is
  *                                   left out reads what an earlier full call left in the same workspace. */
 #define QPG_OPT_TAKES_STAGES 1
+/*   QPG_OPT_NOPHASE_STAGES          which of qpg_match_steps_nophase's two kernels a call launches: bit 0 = the tables, bit
+ *                                   1 = the chase (default 3 = both).  Measurement only (tools/bench_nophase.py times each
+ *                                   between two HIP events): a chase alone follows the tables an earlier full call left in
+ *                                   the same workspace. */
+#define QPG_OPT_NOPHASE_STAGES 2
 #define QPG_OPT_COUNT 4
 int qpg_ctx_set_option(qpg_ctx* ctx, int option, int value);
 int qpg_ctx_get_option(qpg_ctx* ctx, int option, int* value);
@@ -572,6 +577,45 @@ int qpg_fuse_best_ranked(qpg_ctx*, void* stream, const int16_t* rank, const int3
 /* (From how many chains per launch qpg_match_steps_batch deduplicates the gate table by the previous step's winner - one
  * evaluation per DISTINCT winner instead of one per (previous code, vote) state; same table, bit for bit - is the context's
  * QPG_OPT_GATE_DEDUP_FROM_CHAINS: qpg_ctx_set_option.) */
+
+/* The walk WITHOUT the phase gate: the `not use_phase` branches of search_code_knn (GestureKNN.py:578-592) and the window
+ * loop around them (:785-813), for n_chains independent clips of M windows x `steps` steps whose steps sit back to back in
+ * the tables, as in qpg_match_steps_batch.  The tables and the database arguments are qpg_match_steps' (no phase track, no
+ * phase slots).  Per step, with p the previous code (the chain's seed code at its first step, :466-467 / :517-520):
+ *   pos_score = pos_rank[p] + freq_rank * 0.05                                                          (:540-545)
+ *   QPG_MODE_AUD_TXT  combined = (pos_score + aud_rank[q]) + txt_rank[q]; c* = the code at position desired_k of the
+ *                     sorted order; the 4 codes of the AUDIO candidate aud_idx[q][c*] are appended if the step's coin is
+ *                     nonzero (`np.random.rand() > 0.5`), those of the TEXT candidate txt_idx[q][c*] otherwise (:578-586)
+ *   QPG_MODE_AUD      combined = pos_score + aud_rank[q]; the audio candidate of c*, no coin                (:587-589)
+ *   QPG_MODE_TXT      combined = pos_score + txt_rank[q]; the text candidate of c*, no coin.  (The reference indexes
+ *                     aud_index_cands there, :591, a name that does not exist in that branch; this is the evident intent.)
+ * all in float64 in that order of operations.  Equal scores are ordered by code index (the gated walk's rule; np.argsort
+ * leaves their order open): position k is the k-th element of the order by (score, code).  0 <= desired_k <
+ * QPG_NOPHASE_KMAX.  The next step's previous code is the 4th code of the appended block; a window keeps the first
+ * min(4 steps, 30) of its codes and the next window starts from the last KEPT one (motion_output[-1][-1], :791-806), which
+ * must come from the window's last step - a geometry where it does not (or Q per chain > 2048, or tables beyond the LDS)
+ * returns QPG_EUNSUP before anything is launched.  K % 4 == 0, K <= 1024.
+ *   seed_codes [dev-readable] i32 [n_chains]; coins [dev-readable] u8 [n_chains][M steps], nonzero = audio: required for
+ *   QPG_MODE_AUD_TXT, ignored (may be NULL) otherwise; the tables / grids of a side the mode does not use may be NULL;
+ *   out_codes i32 [n_chains][M][min(4 steps, 30)]; out_side i32 [n_chains][M steps]: 0 audio / 1 text;
+ *   out_cand i32 [n_chains][M steps]: the appended candidate j x G + g (which database window and grid position the block
+ *   came from); chain c's status pair at out_status + c x status_stride (>= 2), written last behind a system-scope fence:
+ *   [0] = 1 if the chain reached a code without a candidate (the reference appends nothing there and returns a ragged
+ *   result) or a seed / payload code outside [0, K) - the chain stops, the steps behind it hold -1 -, [1] = *guard_flags;
+ *   workspace [dev], qpg_match_steps_nophase_ws_bytes(n_chains, M, steps, K) bytes: next u16 [Q][2][K] (Q = n_chains M
+ *   steps; [q][s][p]: the previous code after step q when side s, 0 audio / 1 text, is taken from previous code p; 0xFFFF:
+ *   none) followed by pick i32 [Q][2][K] (that side's candidate of c*, -1: none); a side the mode does not use holds
+ *   0xFFFF / -1.  M == 0 writes the status pairs only.
+ * Two launches: the tables for every (step, previous code), then one block per chain that follows next through LDS. */
+#define QPG_NOPHASE_KMAX 16
+size_t qpg_match_steps_nophase_ws_bytes(int n_chains, int M, int steps, int K);
+int qpg_match_steps_nophase(qpg_ctx*, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
+                            const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
+                            const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx, int Ga,
+                            const int32_t* txt_cidx, int Gt, int mode, int desired_k, int M, int steps, int K, int n_chains,
+                            const int32_t* seed_codes, const uint8_t* coins, int32_t* out_codes, int32_t* out_side,
+                            int32_t* out_cand, int32_t* out_status, int64_t status_stride, const int32_t* guard_flags,
+                            void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Library-owned collectives of the row-sharded matcher (round 5).  The reference has no

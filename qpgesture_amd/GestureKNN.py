@@ -16,7 +16,14 @@ code first, deterministic, ranks taken on the device), --n_takes S (default 1: t
 for byte; S > 1: the clip is matched as with 1, then S - 1 further seeds are drawn from np.random - what S - 1 further runs
 of the reference's loop would draw - and all S takes are walked from the tables that produced `knn_pred`, in one set of
 launches (CodeKNN.walk_takes); the file gains `knn_pred_takes` int64 (S, M, 30) with take 0 == `knn_pred`,
-`take_seed_codes` (S,) and `take_first_shared_code` (S,): from which code on a take repeats an earlier one).
+`take_seed_codes` (S,) and `take_first_shared_code` (S,): from which code on a take repeats an earlier one),
+--no_phase (the reference's matching WITHOUT the phase gate, its `not use_phase` branches :578-592 - the paper's "without
+phase guidance" ablation; --mode keeps choosing the modalities: with both, the three rank rows are summed and a coin per
+step, `np.random.rand() > 0.5` drawn behind the seed, takes the audio or the text candidate; `text` builds the evident
+intent of :590-592, which names a variable that does not exist there.  -k / --desired_k, the position of the fused order
+that is taken, is honoured together with --no_phase only - the reference's phase branches ignore it too, so every file
+written without --no_phase is unchanged.  The file gains `knn_sides` int32 (M, steps): 0 audio / 1 text, and `knn_cand`
+int32 (M, steps): the database candidate j * G + g every block came from.  Not with --n_takes > 1).
 """
 import argparse
 import os
@@ -59,6 +66,9 @@ def build_parser():
                    help="matched clips to write, each from its own init_code_phase() draw (take 0 is knn_pred); seeds that "
                         "lead the walk into the same state give the same gesture from there on: the number of DISTINCT takes "
                         "is printed")
+    p.add_argument('--no_phase', action='store_true',
+                   help="match without the phase gate (GestureKNN.py:578-592): position --desired_k of the fused order, a "
+                        "coin per step between the audio and the text candidate.  Not with --n_takes > 1")
     p.add_argument('--db_cache', choices=["auto", "off", "refresh"], default="auto",
                    help="prepared-database cache (qpgesture_amd/db_cache.py): the device-resident database this command "
                         "builds from the five database-side files is written once, keyed by their paths, sizes and mtimes, "
@@ -66,6 +76,14 @@ def build_parser():
                         "refresh: rebuild and overwrite; off: never touch the cache directory")
     p.add_argument('--db_cache_dir', type=str, default=None, help="default: $QPG_DB_CACHE_DIR or ~/.cache/qpgesture_amd")
     return p
+
+
+def check_args(parser, args):
+    """What the flags refuse together (before anything is loaded)."""
+    if args.no_phase and int(args.n_takes) > 1:
+        parser.error("--no_phase with --n_takes > 1 is not implemented: the takes are walked by the phase-gated kernels")
+    if args.no_phase and not 0 <= args.desired_k < 16:
+        parser.error("--desired_k must be in [0, 16) with --no_phase")
 
 
 def _tables_have_exact_ties(T):
@@ -116,7 +134,9 @@ def main_codebook(args, maxFrames=0):
                        freq_rank=freq_rank, wavvq=L.train_wavvq if vq else None)
     else:
         L = load_test_side(args.test_data, args.test_wavlm, args.test_wavvq, device=args.device)
-    knn = CodeKNN(db, use_wavlm=not vq, use_wavvq=vq)                            # draws from np.random like :463-464
+    no_phase = bool(getattr(args, "no_phase", False))
+    knn = CodeKNN(db, use_wavlm=not vq, use_wavvq=vq, use_phase=not no_phase,    # draws from np.random like :463-464
+                  desired_k=args.desired_k if no_phase else 0)
     knn.audio_precision = args.audio_precision
     n_test_seq = maxFrames if maxFrames != 0 else L.test_wavvq.shape[0]          # :740
     dev = db.device
@@ -127,22 +147,26 @@ def main_codebook(args, maxFrames=0):
     print('begin search...')
     mode = {"shipped": MODE_AUD_TXT, "audio": MODE_AUD, "text": MODE_TXT, "wavvq": MODE_AUD_TXT,
             "wavvq_audio": MODE_AUD}[args.mode]
-    seed_code, seed_phase = knn.init_code_phase()                                 # (drawn once: :462-473)
+    if no_phase:                                                                  # (:466-467, then a coin per step, :581)
+        seed_code, seed_phase = knn.init_code_phase(), None
+        state = dict(coins=knn.draw_coins(n_test_seq * knn.n_steps()) if mode == MODE_AUD_TXT else None)
+    else:
+        (seed_code, seed_phase), state = knn.init_code_phase(), {}                # (drawn once: :462-473)
     # --tie_rule numpy: the reference ranks both (Q,512) tables with NumPy's UNSTABLE argsort, whose order differs from a
     # stable one only among EQUAL values.  So the clip is matched with the device's stable ranks, the tables are checked for
     # exact ties on the device, and only a clip that has one is ranked again by the reference's own NumPy call on the host
     # (CodeKNN.host_ranks: both tables through the host in the middle of the step).  Real text tracks tie (silent frames
     # share one embedding); continuous features do not.
-    pred_seqs, _, _ = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
-                                     return_tables=True)                           # (re-matches on the uncapped path if flagged)
+    pred_seqs, _, votes = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
+                                         return_tables=True, **state)              # (re-matches on the uncapped path if flagged)
     n_takes = int(getattr(args, "n_takes", 1))
     if n_takes < 1:
         raise ValueError("--n_takes must be >= 1")
     if args.tie_rule == "numpy" and bool(_tables_have_exact_ties(knn.tables)):
         knn.host_ranks = True
         # (several takes: the host-ranked tables are kept - the takes are walked from the tables that produced knn_pred)
-        pred_seqs, _, _ = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
-                                         return_tables=n_takes > 1)
+        pred_seqs, _, votes = knn.match_clip(te_i, te_c, n_test_seq, mode=mode, seed_code=seed_code, seed_phase=seed_phase,
+                                             return_tables=n_takes > 1, **state)
     takes_out = {}
     if n_takes > 1:
         from . import takes
@@ -161,6 +185,9 @@ def main_codebook(args, maxFrames=0):
     if knn.fallbacks:
         print('near-tie guard: a capped re-evaluation list overflowed; the clip was re-matched on the uncapped path')
     print(pred_seqs.shape)
+    if no_phase:
+        picks = knn.last_picks if n_test_seq else np.zeros((0, knn.n_steps()), np.int32)
+        takes_out = dict(knn_sides=np.asarray(votes, np.int32), knn_cand=np.asarray(picks, np.int32))
     np.savez_compressed(args.out_knn_filename, knn_pred=pred_seqs, **takes_out)  # :845
     print('load+prepare %.2fs%s, match %.4fs (%.0f frames/s)' % (t1 - t0, ' (prepared-database cache)' if from_cache else '',
                                                                    t2 - t1, 240 * n_test_seq / (t2 - t1)))
@@ -173,7 +200,9 @@ def main_codebook(args, maxFrames=0):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_args(parser, args)
     os.environ['PYTHONHASHSEED'] = str(seed_value)                               # :19-22
     random.seed(args.seed)
     np.random.seed(args.seed)

@@ -480,6 +480,37 @@ def plan_takes(kn, db, M, steps, n_takes, serial_walk=False):
     return TakesPlan("kernel", "")
 
 
+class NoPhasePlan(NamedTuple):
+    path: str           # "kernel": qpg_match_steps_nophase | "unsupported"
+    for_walk: bool      # what sweep_tables is asked for: always False (fully settled tables, see below)
+    reason: str         # why "unsupported"; for "kernel": why the tables are the settled ones
+
+
+def plan_nophase(kn, db, M, steps, mode, desired_k):
+    """How a matcher without the phase gate (CodeKNN(use_phase=False)) matches a clip of M windows x `steps` steps.
+    The walk-relevance cut (AudioPlan.cut_top_n) and the prefused gate tables (StepPlan.split_fuse) never feed this walk:
+    the cut proves that a code cannot take the first (or first two) places of the TWO-way fusion pos + rank, and the
+    three-way winner (pos + aud + txt) and position desired_k are outside that proof - so the tables are always those of
+    sweep_tables(for_walk=False), exact everywhere.  Row shards are not implemented; the geometry conditions are the
+    library's (walk_geom, csrc/qpg_tail.hip: QPG_EUNSUP for the same cases)."""
+    if mode not in (MODE_AUD_TXT, MODE_AUD, MODE_TXT):
+        return NoPhasePlan("unsupported", False, "mode %r is not one of MODE_AUD_TXT / MODE_AUD / MODE_TXT" % (mode,))
+    if db.world > 1 or kn.force_sharded:
+        return NoPhasePlan("unsupported", False, "matching without the phase gate on a row-sharded database is not "
+                                                 "implemented (the merged tables would serve; nothing tests them)")
+    if not 0 <= desired_k < min(_lib.QPG_NOPHASE_KMAX, db.K):
+        return NoPhasePlan("unsupported", False, "desired_k %d outside [0, %d)" % (desired_k, _lib.QPG_NOPHASE_KMAX))
+    K = db.K
+    last_idx = min(steps * 4, num_frames_code) - 1
+    if (steps < 1 or steps * 4 > 64 or K % 4 or K > 1024 or last_idx // 4 != steps - 1 or M * steps > 2048 or
+            2 * steps * 2 * K * 2 > 64 * 1024 or (steps * 2 * K) % 8):
+        return NoPhasePlan("unsupported", False, "the tabulated walk does not take this geometry (steps = %d, K = %d, %d "
+                                                 "steps per clip)" % (steps, K, M * steps))
+    return NoPhasePlan("kernel", False, "the walk-relevance cut covers the two-way fusion's first places only: position "
+                                        "%d of the %s-way order reads fully settled tables"
+                       % (desired_k, "three" if mode == MODE_AUD_TXT else "two"))
+
+
 # what CodeKNN._sweep_audio leaves: the per-shard (not yet reduced) tables, the sweep's matrix, the packed queries (the
 # sharded merge re-evaluates requested pairs from them) and the AudioPlan that was carried out
 AudioResult = namedtuple("AudioResult", "dist idx rank D q32 qn2 plan")
@@ -495,7 +526,10 @@ def _grown(buf, nbytes, dev, zero=False):
 class CodeKNN:
     """Mirror of the reference's CodeKNN (GestureKNN.py:422-721) over a GestureDB."""
 
-    def __init__(self, db, use_wavlm=True, use_wavvq=False, use_phase=True, use_txt=True, rng=None):
+    def __init__(self, db, use_wavlm=True, use_wavvq=False, use_phase=True, use_txt=True, rng=None, desired_k=0):
+        """use_phase=False: the reference's matching without the phase gate (GestureKNN.py:578-592):
+        position `desired_k` of the fused order, a coin per step between the audio and the text candidate; match_clip then
+        returns (codes, phases [M,0,8,16], sides).  desired_k is read by such a matcher only (as in the reference)."""
         if use_wavlm == use_wavvq:
             raise ValueError("exactly one of use_wavlm / use_wavvq (GestureKNN.py:431-438)")
         if use_wavvq and not db.has_wavvq:
@@ -508,6 +542,10 @@ class CodeKNN:
             self.step_sz, self.n_db_frm = db.step_sz, db.T
         self.n_db_seq = db.N
         self.use_phase, self.use_txt = use_phase, use_txt
+        if not use_phase and not 0 <= int(desired_k) < _lib.QPG_NOPHASE_KMAX:
+            raise ValueError("desired_k must be in [0, %d) (got %r)" % (_lib.QPG_NOPHASE_KMAX, desired_k))
+        self.desired_k = int(desired_k)
+        self.last_picks = None              # no-phase matcher: the candidate j * G + g every step appended, i32 [M, steps]
         self.rng = rng if rng is not None else np.random
         self.overlap_sweeps = True          # text sweep on a second HIP stream underneath the audio sweep
         self.text_after_sweep = True        # ... started when the audio sweep ends, i.e. underneath the audio SELECT ...
@@ -571,7 +609,8 @@ class CodeKNN:
         # state that appears with use: caches per shape / clip length / knobs, the side stream and its events, grown buffers
         self._qpos, self._qcache, self._layouts, self._mm_cache, self._pinned_ints, self._plans = None, {}, {}, {}, {}, {}
         self._side_stream = self._side_gate = self._side_done = self._sweep_event = None
-        self._mix_ws = self._exact_ws = self._hl_qimage = self._takes_ws = None
+        self._mix_ws = self._exact_ws = self._hl_qimage = self._takes_ws = self._nophase_ws = None
+        self._pinned_nophase = None
         # bench.py: HIP events around the sweep kernel of every kernel_events_every-th call, appended to kernel_events
         # (a list; None: off), taken from kernel_event_pool while it lasts (events created ahead of the timed region)
         self.kernel_events, self.kernel_events_every, self.kernel_event_pool, self._ev_calls = None, 1, None, 0
@@ -617,6 +656,8 @@ class CodeKNN:
         i = self.rng.randint(0, self.n_db_seq)
         j = self.rng.randint(0, self.n_db_frm - int(num_frames / num_frames_code))
         code = int(db.code_host[i, j // num_frames_code])
+        if not self.use_phase:                                     # :466-467: the same two draws, the code alone
+            return code
         P = db.phase_host[i, j:j + 8]                              # (8,2,8)
         if P.shape[0] != 8:
             # wavvq mode draws j up to 389 on a 240-frame phase track (GestureKNN.py:464-469): the reference's
@@ -1205,8 +1246,66 @@ class CodeKNN:
             _lib.call("qpg_match_steps_batch", dev, *head, mode_w, M, steps, db.K, chains, seed, sp, gate, *outs, 2, guard)
         return gate
 
+    def draw_coins(self, n):
+        """The coins of n matching steps of a no-phase clip: `np.random.rand() > 0.5` per step (GestureKNN.py:581) - n
+        successive draws from the matcher's rng, True = the audio candidate."""
+        return np.asarray(self.rng.rand(int(n))).reshape(-1) > 0.5
+
+    def _refuse_nophase(self, what):
+        if not self.use_phase:
+            raise NotImplementedError("%s is not implemented for a matcher without the phase gate (use_phase=False): "
+                                      "match_clip / walk are" % what)
+
+    def _walk_nophase(self, T, n_windows, window_offset, mode, seed_code, coins):
+        """walk() of a matcher without the phase gate: qpg_match_steps_nophase over the tables' rows (two launches).  The
+        seed code and the coins are read from, and the integer results written to, ONE pinned host buffer (zero-copy; the
+        status pair is the walk's last store).  -> (codes int64 [M, 30], phases f32 [M, 0, 8, 16], sides i32 [M, steps]);
+        last_picks = the appended candidates i32 [M, steps]."""
+        db, dev = self.db, self.db.device
+        M, steps, K = int(n_windows), self.n_steps(), self.db.K
+        plan = plan_nophase(self._knobs(), self._facts(), M, steps, mode, self.desired_k)
+        if plan.path != "kernel":
+            raise NotImplementedError(plan.reason)
+        Q, cpw = M * steps, min(4 * steps, num_frames_code)
+        if seed_code is None:
+            seed_code = self.init_code_phase()
+        if not 0 <= int(seed_code) < K:
+            raise ValueError("seed code %r outside [0, %d)" % (seed_code, K))
+        if mode == MODE_AUD_TXT:
+            if coins is None:
+                coins = self.draw_coins(Q)
+            coins = np.asarray(coins).reshape(-1) != 0
+            if coins.size != Q:
+                raise ValueError("coins: one per matching step (%d), got %d" % (Q, coins.size))
+        n_in, n_out = 1 + (Q + 3) // 4, M * cpw + 2 * Q + 2           # seed | coins (u8) || codes | sides | cands | status
+        pin = self._pinned_nophase              # ONE pinned buffer, grown to the longest clip seen (this call drains it)
+        if pin is None or pin.numel() < n_in + n_out:
+            pin = self._pinned_nophase = torch.empty((n_in + n_out,), dtype=torch.int32).pin_memory()
+        pin_np = pin.numpy()
+        pin_np[0] = int(seed_code)
+        if mode == MODE_AUD_TXT:
+            pin_np[1:n_in].view(np.uint8)[:Q] = coins
+        out_np = pin_np[n_in:n_in + n_out]
+        out_np.fill(_PIN_SENTINEL)
+        base = pin.data_ptr()
+        o_codes = base + 4 * n_in
+        o_side, o_cand, o_status = o_codes + 4 * M * cpw, o_codes + 4 * (M * cpw + Q), o_codes + 4 * (M * cpw + 2 * Q)
+        ws = self._nophase_ws = _grown(self._nophase_ws,
+                                       int(_lib.load().qpg_match_steps_nophase_ws_bytes(1, max(M, 1), steps, K)), dev)
+        q0 = window_offset * steps
+        tabs = [None if T[k] is None else T[k][q0:q0 + Q] for k in ("aud_rank", "aud_idx", "txt_rank", "txt_idx")]
+        a_cidx, _, a_G = self._audio_grid()
+        _lib.call("qpg_match_steps_nophase", dev, *tabs, db.pos_rank, db.freq_rank, db.code, db.code.shape[1], a_cidx, a_G,
+                  db.txt_cidx, db.Gt, mode, self.desired_k, M, steps, K, 1, base, base + 4 if mode == MODE_AUD_TXT else None,
+                  o_codes, o_side, o_cand, o_status, 2, self._guard_stats[1:2], ws, ws.numel())
+        ints = _wait_pinned(out_np, torch.cuda.current_stream(dev))
+        self.check_status(ints[-2:])
+        self.last_picks = ints[M * cpw + Q:M * cpw + 2 * Q].reshape(M, steps).copy()
+        codes = ints[:M * cpw].reshape(M, cpw).astype(np.int64)
+        return codes, np.zeros((M, 0, 8, 16), np.float32), ints[M * cpw:M * cpw + Q].reshape(M, steps).copy()
+
     def walk(self, T, n_windows, window_offset=0, mode=MODE_AUD_TXT, seed_code=None, seed_phase=None, sync=True,
-             seed_ptrs=None, out_pin=None, n_chains=1):
+             seed_ptrs=None, out_pin=None, n_chains=1, coins=None):
         """Device-side walk of windows [window_offset, window_offset+n_windows) of the tables.
         sync=True: (codes, phases, votes) as NumPy arrays; sync=False: device tensors (+ the status pair), nothing waited
         for, `_last_ints` = codes | votes | status on the device; sync="ints": the integer results only, as ONE host array
@@ -1223,6 +1322,11 @@ class CodeKNN:
         db, dev = self.db, self.db.device
         M, steps = n_windows, self.n_steps()
         CL = int(n_chains)
+        if not self.use_phase:
+            # (GestureKNN.py:578-592: coins [M * steps], True / nonzero = the audio candidate; drawn here if not given)
+            if sync is not True or seed_ptrs is not None or out_pin is not None or CL != 1:
+                self._refuse_nophase("walk(sync=%r, seed_ptrs, out_pin, n_chains)" % (sync,))
+            return self._walk_nophase(T, n_windows, window_offset, mode, seed_code, coins)
         assert CL == 1 or (seed_ptrs is not None and out_pin is not None), "several chains: the graph path only"
         if seed_ptrs is not None:
             sp = int(seed_ptrs[1])
@@ -1320,6 +1424,7 @@ class CodeKNN:
         seed_ptrs / out_pin / n_takes (ClipGraph): seeds read from, integer results written to pinned host memory, in
         walk()'s several-chains layout with takes in the place of clips."""
         from . import takes
+        self._refuse_nophase("walk_takes")
         return takes.walk_takes(self, T, n_windows, seed_codes, seed_phases, mode, window_offset, sync, seed_ptrs, out_pin,
                                 n_takes)
 
@@ -1331,6 +1436,7 @@ class CodeKNN:
         routes, and walks all takes from them.  Returns a takes.TakesResult: codes, phases, votes, seed_codes,
         first_shared_code (from which code on a take repeats an earlier one) and n_distinct."""
         from . import takes
+        self._refuse_nophase("match_clip_takes")
         return takes.match_clip_takes(self, test_interp, test_context, n_windows, n_takes, seed_codes, seed_phases, mode)
 
     @staticmethod
@@ -1358,37 +1464,58 @@ class CodeKNN:
         and results in the several-clips layout with takes in the place of clips (ClipGraph.run_takes / run_ints).  One GPU,
         n_clips == 1, no encode leg, no doorbell.  With the default the capture is unchanged, node for node."""
         from .replay import ClipGraph
+        self._refuse_nophase("capture_clip_graph")
         return ClipGraph(self, n_windows, mode, n_sweep_windows or n_windows * n_clips, window_offset, audio, context,
                          owner_blocks, n_clips, encoder, encode_input, encode_precision, sweep_signal, doorbell, n_takes)
 
     def _tables_and_walk(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables,
-                         for_walk=False):
+                         for_walk=False, coins=None):
+        if not self.use_phase:
+            for_walk = False                # (plan_nophase: the walk-relevance cut and the prefused tables never feed this walk)
         T = self.sweep_tables(test_interp, test_context, n_windows, mode, for_walk=for_walk)
         if return_tables:
             self.tables = T
+        if not self.use_phase:
+            return self.walk(T, n_windows, 0, mode, seed_code, coins=coins)
         return self.walk(T, n_windows, 0, mode, seed_code, seed_phase)
 
     def match_clip(self, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, seed_code=None,
-                   seed_phase=None, return_tables=False):
+                   seed_phase=None, return_tables=False, coins=None):
         """All windows of one clip: two batched sweeps + rank kernels + one device-side tail walk.
         Returns (codes int64 [M,30], phases f32 [M,8,8,16], votes [M,8]) as NumPy arrays.
         A clip for which the capped near-tie machinery raised its trouble word (GuardOverflow) is matched again on
-        the uncapped path before anything is returned (on a sharded DB every rank sees the same word and re-matches)."""
-        if seed_code is None:                       # drawn ONCE: a re-match starts from the same state
+        the uncapped path before anything is returned (on a sharded DB every rank sees the same word and re-matches).
+        A matcher without the phase gate (use_phase=False) returns (codes int64 [M,30], phases f32 [M,0,8,16], sides i32
+        [M,steps]: 0 audio / 1 text) and keeps the appended candidates as last_picks; its state is the seed code and, with
+        both modalities on, the clip's M * steps coins (`coins`; drawn from the rng behind the seed if not given, like
+        that many successive rand() calls of the reference's loop)."""
+        coins_kw = {}
+        if not self.use_phase:
+            plan = plan_nophase(self._knobs(), self._facts(), n_windows, self.n_steps(), mode, self.desired_k)
+            if plan.path != "kernel":
+                raise NotImplementedError(plan.reason)
+            if seed_code is None:                   # seed, then coins, both drawn ONCE: a re-match replays them
+                seed_code = self.init_code_phase()
+            if coins is None and mode == MODE_AUD_TXT:
+                coins = self.draw_coins(n_windows * self.n_steps())
+            seed_phase, coins_kw = None, dict(coins=coins)
+        elif seed_code is None:                     # drawn ONCE: a re-match starts from the same state
             seed_code, seed_phase = self.init_code_phase()
         if n_windows == 0:                          # an empty clip (the reference's loop body never runs, :785)
-            return (np.zeros((0, num_frames_code), np.int64), np.zeros((0, self.n_steps(), 8, 16), np.float32),
+            n_blocks = self.n_steps() if self.use_phase else 0
+            return (np.zeros((0, num_frames_code), np.int64), np.zeros((0, n_blocks, 8, 16), np.float32),
                     np.zeros((0, self.n_steps()), np.int32))
         clip = (test_interp.contiguous(), test_context, n_windows, mode, seed_code, seed_phase, return_tables)
         try:
-            return self._tables_and_walk(*clip, for_walk=not return_tables)
+            return self._tables_and_walk(*clip, for_walk=not return_tables, **coins_kw)
         except GuardOverflow as e:
             if self.audio_precision == "exact":
                 self.clear_flags()          # (the sticky word must not poison the clips after this one)
                 raise RuntimeError("the uncapped path raised flags 0x%x: this is a bug" % e.flags)
-            return self.rematch(e.flags, *clip)
+            return self.rematch(e.flags, *clip, **coins_kw)
 
-    def rematch(self, flags, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False):
+    def rematch(self, flags, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False,
+                coins=None):
         """The clip again on a path that cannot raise `flags`: only the text prefilter overflowed (FLAG_TEXT_OVERFLOW alone)
         -> the same audio path with the text side on the exact-order sweep; anything else -> audio_precision "exact"
         (f64 sweep + uncapped guard, which also takes the exact-order text sweep).  Clears the trouble word."""
@@ -1399,30 +1526,34 @@ class CodeKNN:
             self.text_fallbacks += 1
             self.text_kernel = "valu"
             try:
-                return self._tables_and_walk(*clip)
+                return self._tables_and_walk(*clip, coins=coins)
             except GuardOverflow:               # the audio side of this clip is in trouble as well
-                return self.rematch_exact(*clip)
+                return self.rematch_exact(*clip, coins=coins)
             finally:
                 self.text_kernel = "mfma"
-        return self.rematch_exact(*clip)
+        return self.rematch_exact(*clip, coins=coins)
 
-    def rematch_exact(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False):
+    def rematch_exact(self, test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables=False,
+                      coins=None):
         """The clip again with audio_precision "exact" (f64 sweep + uncapped guard); clears the trouble word."""
         prev = self.audio_precision
         self.clear_flags()
         self.audio_precision = "exact"
         self.fallbacks += 1
         try:
-            return self._tables_and_walk(test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables)
+            return self._tables_and_walk(test_interp, test_context, n_windows, mode, seed_code, seed_phase, return_tables,
+                                         coins=coins)
         finally:
             self.audio_precision = prev
 
 
 
 
-def predict_code_from_audio(db, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, rng=None):
-    """predict_code_from_audio (GestureKNN.py:724-813) for the shipped flags; returns (M,30) int64."""
-    knn = CodeKNN(db, rng=rng)
+def predict_code_from_audio(db, test_interp, test_context, n_windows, mode=MODE_AUD_TXT, rng=None, use_phase=True,
+                            desired_k=0):
+    """predict_code_from_audio (GestureKNN.py:724-813) for the shipped flags (use_phase=False: without the phase gate, at
+    position desired_k, :578-592); returns (M,30) int64."""
+    knn = CodeKNN(db, rng=rng, use_phase=use_phase, desired_k=desired_k)
     codes, _, _ = knn.match_clip(test_interp, test_context, n_windows, mode=mode)
     return codes
 

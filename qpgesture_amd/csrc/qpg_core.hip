@@ -58,6 +58,7 @@ extern "C" int qpg_ctx_create(int device, qpg_ctx** out) {
   for (int i = 0; i < QPG_OPT_COUNT; ++i) c->opt[i] = 0;
   c->opt[QPG_OPT_GATE_DEDUP_FROM_CHAINS] = 1;
   c->opt[QPG_OPT_TAKES_STAGES] = 7;
+  c->opt[QPG_OPT_NOPHASE_STAGES] = 3;
   int prev = 0;
   (void)hipGetDevice(&prev);
   const bool ok = hipSetDevice(device) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&c->zeros), 4096) == hipSuccess &&

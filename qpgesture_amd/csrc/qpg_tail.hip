@@ -284,14 +284,17 @@ struct TailArgs {
 // The last stores of a walk, by the whole block.  The status pair is written LAST and behind a system-scope fence: when
 // the outputs live in pinned host memory (the matcher's zero-copy results) a host that sees the pair also sees the codes
 // and votes of every thread above.  `bad`: a register of thread 0 or a block-shared word, read behind the barrier.
-__device__ __forceinline__ void write_status_pair(const TailArgs& A, const int& bad) {
+__device__ __forceinline__ void write_status_pair(int32_t* out_status, const int32_t* guard_flags, const int& bad) {
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
-    A.out_status[0] = bad;
+    out_status[0] = bad;
     __threadfence_system();
-    A.out_status[1] = A.guard_flags ? A.guard_flags[0] : 0;
+    out_status[1] = guard_flags ? guard_flags[0] : 0;
   }
+}
+__device__ __forceinline__ void write_status_pair(const TailArgs& A, const int& bad) {
+  write_status_pair(A.out_status, A.guard_flags, bad);
 }
 
 // The state a chain's first step starts from: its seed code -> *p, its seed phase block (128 floats) returned.
@@ -796,6 +799,258 @@ __global__ void status_only_kernel(int32_t* out_status, const int32_t* guard_fla
   out_status[1] = guard_flags ? guard_flags[0] : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The walk WITHOUT the phase gate (search_code_knn(use_phase=False), GestureKNN.py:578-592; qpg_match_steps_nophase).
+// Per step the reference fuses the rank rows - (pos_score + aud_rank) + txt_rank with both sides on (:579), pos_score +
+// rank with one (:575 / :554) -, takes the code at position desired_k of the sorted order and appends the 4 codes of that
+// code's audio or text candidate (both sides on: a coin per step, :581).  The running state is the previous code alone, so
+// the step tabulates like the gated one: for every (step q, previous code p)
+//   c*              = the code at position desired_k of the order by (score, code index)        (nophase_table_kernel)
+//   pick[q][s][p]   = idx_s[q][c*]: the candidate of side s (0 audio, 1 text)
+//   next[q][s][p]   = the code that becomes the previous code when side s is taken (u16; 0xFFFF: no such state)
+// and a chain is Q dependent 2-byte LDS lookups (nophase_chase_kernel).  next is [steps][2][K] u16 per window: the gate
+// table's geometry, staged by chase_windows as it is.
+// ---------------------------------------------------------------------------------------------
+struct NoPhaseArgs {
+  const int16_t* rank0;      // [Q][K] the first rank addend: audio (QPG_MODE_AUD_TXT, _AUD) or text (_TXT)
+  const int16_t* rank1;      // [Q][K] text, QPG_MODE_AUD_TXT only
+  const int32_t* idx_a;      // [Q][K] candidate index per code, side 0 / side 1 (NULL: the mode does not use the side)
+  const int32_t* idx_t;
+  const int16_t* pos_rank;   // [K][K]
+  const int16_t* freq_rank;  // [K]
+  const int32_t* code;       // [N][code_ld]
+  int code_ld;
+  const int32_t* cidx_a;     // [Ga] / [Gt] code column of a grid position
+  int Ga;
+  const int32_t* cidx_t;
+  int Gt;
+  int mode, desired_k, M, steps, K, n_chains, codes_per_window;
+  const int32_t* seed_codes; // [n_chains]
+  const uint8_t* coins;      // [n_chains][M steps], nonzero: audio (QPG_MODE_AUD_TXT only)
+  uint16_t* next;            // [Q][2][K]
+  int32_t* pick;             // [Q][2][K]
+  int32_t* out_codes;        // [n_chains][M][codes_per_window]
+  int32_t* out_side;         // [n_chains][M steps]
+  int32_t* out_cand;         // [n_chains][M steps]
+  int32_t* out_status;       // chain c's pair at c x status_stride
+  int64_t status_stride;
+  const int32_t* guard_flags;
+};
+
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+#define NOPHASE_LIST 128      // short-list entries per (step, previous code): 8 per lane
+
+// the smallest (score, code) of a 16-lane group, on every lane of it
+__device__ __forceinline__ ArgMin group16_argmin(ArgMin m) {
+  m = amin(m, argmin_xchg<8>(m));
+  m = amin(m, argmin_xchg<4>(m));
+  m = amin(m, argmin_xchg<2>(m));
+  return amin(m, argmin_xchg<1>(m));
+}
+
+// One (q, p) per 16-lane group, every code of the row: lane l owns codes 4 (l + 16 i) .. + 3, i < NI (8-byte loads; K % 4
+// == 0, K <= 64 NI), their f64 scores in registers - the rows are read ONCE whatever desired_k is.  Position k is then
+// found by k + 1 rounds - the smallest (score, code) above the previous round's, reduced over the group with DPP moves -
+// over the registers for k = 0 and over a short list of the codes that can be there for k > 0 (below).  No rank row is
+// assumed to be a permutation (every code is scored as the values are).  Lanes 0 / 1 of the group look up side 0 / 1 of
+// the winner.
+template <int NI, bool LIST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) void nophase_table_kernel(NoPhaseArgs A) {
+  const int K = A.K, tid = threadIdx.x, l16 = tid & 15;
+  const int64_t n_task = (int64_t)A.n_chains * A.M * A.steps * K;
+  int64_t task = (int64_t)blockIdx.x * 16 + (tid >> 4);
+  const bool live = task < n_task;
+  if (!live) task = n_task - 1;                                  // (computed, not stored: the group's DPP moves stay whole)
+  const int q = (int)(task / K), p = (int)(task - (int64_t)q * K);
+  const int16_t* pr = A.pos_rank + (int64_t)p * K;
+  const int16_t* r0 = A.rank0 + (int64_t)q * K;
+  const bool three = A.mode == QPG_MODE_AUD_TXT;
+  const int16_t* r1 = three ? A.rank1 + (int64_t)q * K : r0;
+  double v[4 * NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c0 = 4 * (l16 + 16 * i);
+    if (c0 < K) {
+      const i16x4 pv = *reinterpret_cast<const i16x4*>(pr + c0);
+      const i16x4 fv = *reinterpret_cast<const i16x4*>(A.freq_rank + c0);
+      const i16x4 a = *reinterpret_cast<const i16x4*>(r0 + c0);
+      const i16x4 b = *reinterpret_cast<const i16x4*>(r1 + c0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double s = ((double)pv[u] + (double)fv[u] * 0.05) + (double)a[u];      // :540-545, :575 / :554
+        v[4 * i + u] = three ? s + (double)b[u] : s;                                  // :579
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[4 * i + u] = __builtin_inf();
+    }
+  }
+  ArgMin last{-__builtin_inf(), -1};
+  // the smallest (score, code) above `from` among this group's registers, on every lane of the group
+  auto next_of_all = [&](ArgMin from) {
+    ArgMin m{__builtin_inf(), 0x7fffffff};
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = 4 * (l16 + 16 * i) + u;
+        const double s = v[4 * i + u];
+        if (s > from.v || (s == from.v && c > from.i)) m = amin(m, ArgMin{s, c});
+      }
+    }
+    return group16_argmin(m);
+  };
+  if (!LIST || A.desired_k == 0) {
+    // (K > 512, LIST off: 64 scores per lane leave no registers for the list's stages - every round over the registers)
+    for (int r = 0; r <= A.desired_k; ++r) last = next_of_all(last);
+  } else {
+    // k > 0: the k + 1 rounds run over a SHORT list.  Every lane's smallest score is one of 16 different codes' scores,
+    // so at least 16 > k codes score at most U = the largest of the lanes' minima, and positions 0 .. k lie among the
+    // codes with score <= U: a few dozen of K on tables without mass ties.  They are gathered into LDS, at most
+    // NOPHASE_LIST per group; a group with more (mass ties) keeps the registers.
+    __shared__ double ls[16][NOPHASE_LIST];
+    __shared__ short lc[16][NOPHASE_LIST];
+    const int grp = tid >> 4;
+    double lo = __builtin_inf();
+#pragma unroll
+    for (int i = 0; i < 4 * NI; ++i) lo = fmin(lo, v[i]);
+    double U = lo;
+    U = fmax(U, argmin_xchg<8>(ArgMin{U, 0}).v);
+    U = fmax(U, argmin_xchg<4>(ArgMin{U, 0}).v);
+    U = fmax(U, argmin_xchg<2>(ArgMin{U, 0}).v);
+    U = fmax(U, argmin_xchg<1>(ArgMin{U, 0}).v);
+    // how many this lane holds, its offset in the group's list (a butterfly over the 16 lanes) and the list's length
+    int mine = 0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) mine += (4 * (l16 + 16 * i) + u < K && v[4 * i + u] <= U) ? 1 : 0;
+    }
+    int n = mine, at = 0;
+    { const int t = lane_xor<1>(n); at += (l16 & 1) ? t : 0; n += t; }
+    { const int t = lane_xor<2>(n); at += (l16 & 2) ? t : 0; n += t; }
+    { const int t = lane_xor<4>(n); at += (l16 & 4) ? t : 0; n += t; }
+    { const int t = lane_xor<8>(n); at += (l16 & 8) ? t : 0; n += t; }
+    if (n <= NOPHASE_LIST) {
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = 4 * (l16 + 16 * i) + u;
+          if (c < K && v[4 * i + u] <= U) {
+            ls[grp][at] = v[4 * i + u];
+            lc[grp][at] = (short)c;
+            ++at;
+          }
+        }
+      }
+    }
+    // (a group's list is written and read by its own 16 lanes, one wave: the block-wide barrier is more than needed, and
+    //  it is safe because every thread of the block arrives - desired_k is uniform and a group past the last task is
+    //  clamped above, never returned early)
+    __syncthreads();
+    if (n > NOPHASE_LIST) {                                      // (uniform over the group)
+      for (int r = 0; r <= A.desired_k; ++r) last = next_of_all(last);
+    } else {
+      double w[NOPHASE_LIST / 16];
+      int wc[NOPHASE_LIST / 16];
+#pragma unroll
+      for (int j = 0; j < NOPHASE_LIST / 16; ++j) {
+        const int e = 16 * j + l16;
+        w[j] = e < n ? ls[grp][e] : __builtin_inf();
+        wc[j] = e < n ? (int)lc[grp][e] : 0x7fffffff;
+      }
+      for (int r = 0; r <= A.desired_k; ++r) {
+        ArgMin m{__builtin_inf(), 0x7fffffff};
+#pragma unroll
+        for (int j = 0; j < NOPHASE_LIST / 16; ++j)
+          if (w[j] > last.v || (w[j] == last.v && wc[j] > last.i)) m = amin(m, ArgMin{w[j], wc[j]});
+        last = group16_argmin(m);
+      }
+    }
+  }
+  if (live && l16 < 2) {
+    const int s = l16;
+    const bool used = three || (A.mode == QPG_MODE_AUD ? s == 0 : s == 1);
+    int cand = -1;
+    unsigned int nx = 0xFFFFu;
+    if (used && last.i < K) {
+      cand = (s ? A.idx_t : A.idx_a)[(int64_t)q * K + last.i];
+      if (cand >= 0) {
+        const int G = s ? A.Gt : A.Ga;
+        const int j = cand / G, g = cand - j * G;
+        // the 4th code of the block; a window's last step: its last KEPT code (walk_geom's off_last)
+        const int o = (q % A.steps == A.steps - 1) ? (A.codes_per_window - 1) % 4 : 3;
+        const int cv = A.code[(int64_t)j * A.code_ld + (s ? A.cidx_t : A.cidx_a)[g] + o];
+        if ((unsigned)cv < (unsigned)K) nx = (unsigned int)cv;   // (a code outside [0, K) is no state: the chain stops there)
+      } else {
+        cand = -1;
+      }
+    }
+    A.pick[((int64_t)q * 2 + s) * K + p] = cand;
+    A.next[((int64_t)q * 2 + s) * K + p] = (uint16_t)nx;
+  }
+}
+
+// One block per chain.  Thread 0 follows p <- next[q][side[q]][p] through the windows' tables in LDS (chase_windows) and
+// records (p, side) of every step; the block then writes every step's side, candidate and codes, and the status pair last.
+// A step the chain does not reach (behind a 0xFFFF state) gets -1 everywhere: every output word is written.
+__global__ __launch_bounds__(1024) void nophase_chase_kernel(NoPhaseArgs A) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t gl[];     // 2 x [steps][2][K]
+  __shared__ uint16_t trail[QPG_CHASE_QMAX];                        // p | side << 15; 0xFFFF: not reached
+  __shared__ uint8_t side_s[QPG_CHASE_QMAX];
+  __shared__ int bad_s;
+  const int K = A.K, Q = A.M * A.steps, tid = threadIdx.x, nt = blockDim.x;
+  const int per_w = A.steps * 2 * K;
+  const int chain = blockIdx.x;
+  const int64_t q0 = (int64_t)chain * Q;
+  const uint16_t* next = A.next + q0 * 2 * K;
+  const int32_t* pick = A.pick + q0 * 2 * K;
+  int32_t* out_codes = A.out_codes + (int64_t)chain * A.M * A.codes_per_window;
+  int32_t* out_side = A.out_side + q0;
+  int32_t* out_cand = A.out_cand + q0;
+  for (int q = tid; q < Q; q += nt) {
+    side_s[q] = A.mode == QPG_MODE_AUD ? 0 : (A.mode == QPG_MODE_TXT ? 1 : (A.coins[q0 + q] ? 0 : 1));     // :581
+    trail[q] = 0xFFFFu;
+  }
+  if (tid == 0) bad_s = 0;
+  int p = tid == 0 ? A.seed_codes[chain] : 0;
+  bool stop = (unsigned)p >= (unsigned)K;
+  chase_windows(gl, next, A.M, per_w, [&](int w, const uint16_t* g) {
+    if (tid == 0) {
+      for (int s = 0; s < A.steps && !stop; ++s) {
+        const int q = w * A.steps + s, side = side_s[q];
+        trail[q] = (uint16_t)(p | (side << 15));
+        const int n = g[(s * 2 + side) * K + p];
+        if (n >= K) stop = true; else p = n;              // (0xFFFF: no state; anything else >= K is not a table's value)
+      }
+    }
+  });
+  if (tid == 0 && stop) bad_s = 1;
+  for (int q = tid; q < Q; q += nt) {
+    const int t = trail[q];
+    const bool reached = t != 0xFFFF;
+    out_side[q] = reached ? t >> 15 : -1;
+    out_cand[q] = reached ? pick[((int64_t)q * 2 + (t >> 15)) * K + (t & 0x7FFF)] : -1;
+  }
+  for (int i = tid; i < A.M * A.codes_per_window; i += nt) {
+    const int w = i / A.codes_per_window, c = i - w * A.codes_per_window;
+    const int q = w * A.steps + c / 4, t = trail[q];
+    int val = -1;
+    if (t != 0xFFFF) {
+      const int s = t >> 15;
+      const int cand = pick[((int64_t)q * 2 + s) * K + (t & 0x7FFF)];
+      if (cand >= 0) {
+        const int G = s ? A.Gt : A.Ga;
+        const int j = cand / G, g = cand - j * G;
+        val = A.code[(int64_t)j * A.code_ld + (s ? A.cidx_t : A.cidx_a)[g] + (c & 3)];
+      }
+    }
+    out_codes[i] = val;
+  }
+  write_status_pair(A.out_status + (int64_t)chain * A.status_stride, A.guard_flags, bad_s);
+}
+
 // One modality's gate-candidate table, launched behind that modality's select on ITS stream (sweep_tables for the walk):
 // rank i16 [Q][K] (a permutation per row), idx i32 [Q][K], T i32 [Q][K] = the T0 (audio) or T1 (text) region of the walk's
 // gate_tables.  qpg_match_steps* with QPG_MODE_PREFUSED then starts at the gate table.  K % 16 == 0, K <= 4096.
@@ -1051,4 +1306,86 @@ extern "C" int qpg_match_steps_takes(qpg_ctx* ctx, void* stream, const int16_t* 
   a.seed_codes = seed_codes; a.status_stride = status_stride;
   a.n_takes = n_takes; a.takes_ws = workspace; a.takes_ws_bytes = workspace_bytes;
   return match_steps_impl(ctx, stream, a);
+}
+
+// The walk without the phase gate (include/qpg.h has the contract and the arguments): two launches, the table of every
+// (step, previous code) and one chase block per chain.  workspace = next u16 [Q][2][K] | pick i32 [Q][2][K], Q =
+// n_chains x M x steps (next's bytes are a multiple of 16: K % 4 == 0).
+static size_t nophase_next_bytes(int64_t Q, int K) { return ((size_t)Q * 2 * K * sizeof(uint16_t) + 15) & ~(size_t)15; }
+
+extern "C" size_t qpg_match_steps_nophase_ws_bytes(int n_chains, int M, int steps, int K) {
+  if (n_chains < 1 || M < 1 || steps < 1 || K < 1) return 0;
+  const int64_t Q = (int64_t)n_chains * M * steps;
+  return nophase_next_bytes(Q, K) + (size_t)Q * 2 * K * sizeof(int32_t);
+}
+
+extern "C" int qpg_match_steps_nophase(qpg_ctx* ctx, void* stream, const int16_t* aud_rank, const int32_t* aud_idx,
+                                       const int16_t* txt_rank, const int32_t* txt_idx, const int16_t* pos_rank,
+                                       const int16_t* freq_rank, const int32_t* code, int code_ld, const int32_t* aud_cidx,
+                                       int Ga, const int32_t* txt_cidx, int Gt, int mode, int desired_k, int M, int steps,
+                                       int K, int n_chains, const int32_t* seed_codes, const uint8_t* coins,
+                                       int32_t* out_codes, int32_t* out_side, int32_t* out_cand, int32_t* out_status,
+                                       int64_t status_stride, const int32_t* guard_flags, void* workspace,
+                                       size_t workspace_bytes) {
+  QPG_REQUIRE(ctx && pos_rank && freq_rank && code && seed_codes && out_codes && out_side && out_cand && out_status,
+              "qpg_match_steps_nophase: null pointer");
+  QPG_REQUIRE(mode == QPG_MODE_AUD_TXT || mode == QPG_MODE_AUD || mode == QPG_MODE_TXT,
+              "qpg_match_steps_nophase: bad mode %d (QPG_MODE_AUD_TXT, _AUD or _TXT)", mode);
+  QPG_REQUIRE(mode == QPG_MODE_TXT || (aud_rank && aud_idx && aud_cidx && Ga > 0),
+              "qpg_match_steps_nophase: audio tables missing");
+  QPG_REQUIRE(mode == QPG_MODE_AUD || (txt_rank && txt_idx && txt_cidx && Gt > 0),
+              "qpg_match_steps_nophase: text tables missing");
+  QPG_REQUIRE(mode != QPG_MODE_AUD_TXT || coins, "qpg_match_steps_nophase: the two-sided mode needs the coins");
+  QPG_REQUIRE(M >= 0 && steps > 0 && steps * 4 <= 64 && K > 0 && K <= 64 * QPG_KMAX_PER_LANE && (K % 4) == 0 &&
+                  code_ld > 0 && n_chains >= 1 && status_stride >= 2,
+              "qpg_match_steps_nophase: bad size");
+  QPG_REQUIRE(desired_k >= 0 && desired_k < QPG_NOPHASE_KMAX && desired_k < K,
+              "qpg_match_steps_nophase: desired_k %d outside [0, %d)", desired_k, QPG_NOPHASE_KMAX);
+  const int Qc = M * steps;
+  const int64_t Q = (int64_t)Qc * n_chains;
+  QPG_REQUIRE((Q * K + 15) / 16 < 0x7fffffffll, "qpg_match_steps_nophase: too many steps");
+  const WalkGeom geo = walk_geom(false, steps, K, Qc);
+  if (!geo.tabulated) {
+    qpg_set_error("qpg_match_steps_nophase: the tabulated walk does not take this geometry (steps = %d, K = %d, %d steps "
+                  "per chain)", steps, K, Qc);
+    return QPG_EUNSUP;
+  }
+  if (M == 0) {
+    for (int c = 0; c < n_chains; ++c) {
+      hipLaunchKernelGGL(status_only_kernel, dim3(1), dim3(1), 0, qpg_stream(stream), out_status + c * status_stride,
+                         guard_flags);
+      QPG_LAUNCH_CHECK("status_only_kernel");
+    }
+    return QPG_OK;
+  }
+  QPG_REQUIRE(workspace && workspace_bytes >= qpg_match_steps_nophase_ws_bytes(n_chains, M, steps, K),
+              "qpg_match_steps_nophase: workspace too small (qpg_match_steps_nophase_ws_bytes)");
+  const int rc = walk_lds_ok("nophase_chase_kernel", reinterpret_cast<const void*>(nophase_chase_kernel), geo.lds_chase);
+  if (rc != QPG_OK) return rc;
+  NoPhaseArgs A;
+  A.rank0 = mode == QPG_MODE_TXT ? txt_rank : aud_rank;
+  A.rank1 = mode == QPG_MODE_AUD_TXT ? txt_rank : nullptr;
+  A.idx_a = mode == QPG_MODE_TXT ? nullptr : aud_idx;
+  A.idx_t = mode == QPG_MODE_AUD ? nullptr : txt_idx;
+  A.pos_rank = pos_rank; A.freq_rank = freq_rank; A.code = code; A.code_ld = code_ld;
+  A.cidx_a = aud_cidx; A.Ga = Ga; A.cidx_t = txt_cidx; A.Gt = Gt;
+  A.mode = mode; A.desired_k = desired_k; A.M = M; A.steps = steps; A.K = K; A.n_chains = n_chains;
+  A.codes_per_window = geo.codes_per_window;
+  A.seed_codes = seed_codes; A.coins = coins;
+  A.next = reinterpret_cast<uint16_t*>(workspace);
+  A.pick = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + nophase_next_bytes(Q, K));
+  A.out_codes = out_codes; A.out_side = out_side; A.out_cand = out_cand; A.out_status = out_status;
+  A.status_stride = status_stride; A.guard_flags = guard_flags;
+  const dim3 grid((unsigned)((Q * K + 15) / 16));
+  const int stages = ctx->opt[QPG_OPT_NOPHASE_STAGES];                    // (3 unless a measurement asked for less)
+  if (stages & 1) {
+    if (K <= 512) hipLaunchKernelGGL((nophase_table_kernel<8, true>), grid, dim3(256), 0, qpg_stream(stream), A);
+    else hipLaunchKernelGGL((nophase_table_kernel<16, false>), grid, dim3(256), 0, qpg_stream(stream), A);
+    QPG_LAUNCH_CHECK("nophase_table_kernel");
+  }
+  if (stages & 2) {
+    hipLaunchKernelGGL(nophase_chase_kernel, dim3(n_chains), dim3(1024), geo.lds_chase, qpg_stream(stream), A);
+    QPG_LAUNCH_CHECK("nophase_chase_kernel");
+  }
+  return QPG_OK;
 }

@@ -42,14 +42,20 @@ def takes_flags(n_takes=1, takes=None):
         (['--takes', str(takes)] if takes is not None else [])
 
 
+def nophase_flags(no_phase=False, desired_k=0):
+    """GestureKNN's --no_phase / --desired_k: nothing for the defaults."""
+    return (['--no_phase'] if no_phase else []) + (['--desired_k', str(int(desired_k))] if int(desired_k) else [])
+
+
 def main(test_data, config, VQVAE_model_path, output_fold=None, prefix=None, gpu='0', subprocess=False, no_bvh=False,
-         knn_extra=(), n_takes=1, takes=None, **db_paths):
+         knn_extra=(), n_takes=1, takes=None, no_phase=False, desired_k=0, **db_paths):
     """test_data: the utterance's `<name>_norm_mfcc.npz` (inference.py:51-54 writes it).  db_paths: train_database,
     train_codebook, codebook_signature, train_wavlm, test_wavlm (, train_wavvq, test_wavvq) - inference.py:57-65.
     Writes `<output_fold>/knn_pred.npz` and `<output_fold>/result_<name>/generateresult_<name>.npy` (+ the BVH unless
     no_bvh), the reference's file names (:21-23, :68).  Returns (knn_pred int64 (M,30), poses f32 (240 M, 135)).
     n_takes / takes: GestureKNN's --n_takes and VisualizeCodebook's --takes, passed through (several matched clips from one
-    sweep, decoded in one batch; with `takes` the poses returned are the selected takes' (S, 240 M, 135))."""
+    sweep, decoded in one batch; with `takes` the poses returned are the selected takes' (S, 240 M, 135)).
+    no_phase / desired_k: GestureKNN's --no_phase and --desired_k, passed through (matching without the phase gate)."""
     import numpy as np
     name = os.path.basename(test_data)
     for suffix in ('_norm_mfcc.npz', '_mfcc.npz', '.npz'):
@@ -59,7 +65,8 @@ def main(test_data, config, VQVAE_model_path, output_fold=None, prefix=None, gpu
     output_fold = output_fold or os.path.dirname(os.path.abspath(test_data))
     os.makedirs(output_fold, exist_ok=True)
     out_knn = os.path.join(output_fold, 'knn_pred.npz')
-    argv = knn_command(test_data, out_knn, extra=list(knn_extra) + takes_flags(n_takes, None), **db_paths)
+    argv = knn_command(test_data, out_knn, extra=list(knn_extra) + takes_flags(n_takes, None) +
+                       nophase_flags(no_phase, desired_k), **db_paths)
     if subprocess:                                               # inference.py:66 subprocess.call(cmd)
         rc = _subprocess.call([sys.executable, '-m', 'qpgesture_amd.GestureKNN'] + argv)
         if rc != 0:
@@ -89,6 +96,8 @@ def build_parser():
     p.add_argument('--subprocess', action='store_true', help='run GestureKNN as a child process, as the reference does')
     p.add_argument('--no_bvh', action='store_true')
     p.add_argument('--n_takes', type=int, default=1, help='GestureKNN --n_takes: matched clips per utterance')
+    p.add_argument('--no_phase', action='store_true', help='GestureKNN --no_phase: match without the phase gate')
+    p.add_argument('--desired_k', type=int, default=0, help='GestureKNN --desired_k (read with --no_phase only)')
     p.add_argument('--takes', default=None, help="VisualizeCodebook --takes: 'all' or a take's index")
     return p
 

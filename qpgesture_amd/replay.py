@@ -29,6 +29,7 @@ class ClipGraph:
     def __init__(self, knn, n_windows, mode, n_sweep_windows, window_offset, audio=None, context=None, owner_blocks=False,
                  n_clips=1, encoder=None, encode_input=None, encode_precision="f32", sweep_signal=False, doorbell=False,
                  n_takes=1):
+        knn._refuse_nophase("ClipGraph (capture_clip_graph)")
         db, dev = knn.db, knn.db.device
         self.owner_blocks = owner_blocks
         # n_takes > 1: ONE clip per replay, walked from n_takes seeds behind its one sweep
@@ -447,6 +448,9 @@ class ClipPipeline:
     def __init__(self, db, depth=2, rng=None, **knn_flags):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        if not knn_flags.get("use_phase", True):
+            raise NotImplementedError("ClipPipeline is not implemented for matching without the phase gate "
+                                      "(use_phase=False): CodeKNN.match_clip is")
         self.db = db
         self.lanes = []
         for _ in range(depth):
@@ -601,6 +605,9 @@ class GraphPipeline:
     def __init__(self, db, n_windows, clips_per_replay=4, depth=2, mode=MODE_AUD_TXT, rng=None, stagger=True, **knn_flags):
         if depth < 1 or clips_per_replay < 1:
             raise ValueError("depth and clips_per_replay must be >= 1")
+        if not knn_flags.get("use_phase", True):
+            raise NotImplementedError("GraphPipeline is not implemented for matching without the phase gate "
+                                      "(use_phase=False): CodeKNN.match_clip is")
         if db.world != 1:
             raise NotImplementedError("GraphPipeline: one GPU holding the whole database (clip-parallel across GPUs: one "
                                       "pipeline per rank, bench.py --scaling replicated)")
