@@ -18,6 +18,7 @@ import pytest
 
 from tests import select_ref as R
 from tests.helpers import merge_mixed_by_hand
+from tests.prefilter_ref import mask_rule
 
 pytestmark = pytest.mark.gpu
 
@@ -341,9 +342,9 @@ def _text_select(form, Dm_in, band, Q, idx_base=0):
     Dm_in = np.ascontiguousarray(Dm_in[:Q])
     tiles = Dm_in.reshape(Q, nt, 16)
     tmin = tiles.min(axis=2)
-    # the rule tests/test_gpu_cfg3.py states for the GEMM's masks: bit r iff Dm[r] <= tile minimum + f32(band), in f32
-    mask = (tiles <= (tmin[:, :, None] + np.float32(band))).astype(np.uint16)
-    mask = (mask << np.arange(16, dtype=np.uint16)).sum(axis=2).astype(np.uint16)
+    # the GEMMs' rule (tests/prefilter_ref.py, held against the kernels by tests/test_gpu_prefilter_contract.py): bit r iff
+    # Dm[r] <= tile minimum + f32(band), in f32
+    mask = mask_rule(Dm_in, band)
     # what the select's rule lists from these inputs (by-query / by-code forms agree): opened tiles' rows, padding never
     seg = t.layout[2]
     cmin = np.full((Q, t.K), np.inf, np.float32)
