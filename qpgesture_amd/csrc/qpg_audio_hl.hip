@@ -130,14 +130,106 @@ __global__ void hl_exponent_kernel(const unsigned int* __restrict__ amax_bits, i
   meta[0] = hl_exponent(__uint_as_float(amax_bits[0]));
 }
 
+// ---- the image format, stated once: every pack kernel below is written in these ---------------------------------------
+// Block-wide max |x| -> scale exponent: m is the thread's partial maximum, the result hl_exponent(block maximum) on every
+// thread.  NW = waves of the block (blockDim.x / 64); every thread calls it (two barriers).  Whether a live query stores its
+// exponent is the caller's business.
+template <int NW>
+__device__ __forceinline__ int hl_block_exponent(float m) {
+  __shared__ float red[NW];
+  __shared__ int e_s;
+  const int tid = threadIdx.x;
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < NW; ++i) m = fmaxf(m, red[i]);
+    e_s = hl_exponent(m);
+  }
+  __syncthreads();
+  return e_s;
+}
+
+// Eight consecutive values (v0 | v1), scaled by sc = 2^e, -> one 16-byte h piece and one l piece.  AUDIO: split_hl_audio
+// (l at its true scale: the audio images), else split_hl (l 2^11: the row and column images).
+template <bool AUDIO>
+__device__ __forceinline__ void hl_split8(f32x4 v0, f32x4 v1, float sc, h8& hh, h8& ll) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    _Float16 a0, b0, a1, b1;
+    if (AUDIO) {
+      split_hl_audio(v0[e] * sc, a0, b0);
+      split_hl_audio(v1[e] * sc, a1, b1);
+    } else {
+      split_hl(v0[e] * sc, a0, b0);
+      split_hl(v1[e] * sc, a1, b1);
+    }
+    hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
+  }
+}
+// ... of eight consecutive floats at p (16-byte aligned; the normalised row in LDS)
+template <bool AUDIO>
+__device__ __forceinline__ void hl_split8(const float* p, float sc, h8& hh, h8& ll) {
+  hl_split8<AUDIO>(reinterpret_cast<const f32x4*>(p)[0], reinterpret_cast<const f32x4*>(p)[1], sc, hh, ll);
+}
+
+// THE COLUMN-IMAGE LAYOUT (audio query image and generic column image): the h and the l piece of elements k .. k + 7
+// (k % 8 == 0) of query slot q.
+//   image[((((chunk*KB + kb)*6 + ct)*2 + plane)*64 + lane][8],   chunk = q / QC, kb = k / 32,
+//   ct = ct0 + (q % QC) / 16, lane = q % 16 + 16 * ((k % 32) / 8).
+// Audio: QC = 48 (HL_QC), ct0 = half * 3, element k of half `half` = q32[q][half*3F + k] (column tiles 0..2 = the first
+// three taps, 3..5 = the last three).  Generic: QC = 96 (HL_GQC), ct0 = 0.  Slots >= Q are written as zero pieces: chunks
+// are always QC wide.  The per-query exponents qexp[chunks*QC] sit behind the fragments (hl_audio_query_view /
+// hl_cols_view).
+__device__ __forceinline__ void hl_store_col_piece(_Float16* __restrict__ image, int q, int QC, int KB, int k, int ct0,
+                                                   h8 hh, h8 ll) {
+  const int chunk = q / QC, qq = q % QC;
+  const int kb = k / 32, ct = ct0 + qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
+  const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
+  reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
+  reinterpret_cast<h8*>(image)[(piece + 1) * 64 + lane] = ll;
+}
+
 // ---- database image ------------------------------------------------------------------------------------------------
 // thread <-> (window j, super-row i < 27, k8 = k / 8): reads 8 consecutive features, writes one 16-byte h piece and one
-// l piece.  DENSE image: a window is [tile 0: KB x 2 planes x 64 units][tile 1: KB x 2 planes x 44 units] of 16 bytes;
+// l piece.  DENSE image: a window is [tile 0: KB x PL planes x 64 units][tile 1: KB x PL planes x 44 units] of 16 bytes;
 // tile 0 (rows 0..15): unit = lane = i + 16 * ((k % 32) / 8); tile 1 (rows 16..26, 11 live of 16): unit = 11 * ((k % 32)
 // / 8) + (i - 16).  (The first layout kept 64 units for tile 1 too and never loaded rows 27..31 - but their 16-byte slots
 // sat inside the 128-byte lines the live rows pulled in: PMC fetch 1.21 x the algorithmic bytes.)
 #define HL_T1_UNITS 44        // 16-byte units of a tile-1 fragment: 11 live rows x 4 k-groups
 #define HL_WIN_UNITS(KB) ((int64_t)(KB) * 2 * (64 + HL_T1_UNITS))
+#define HL1_WIN_UNITS(KB) ((int64_t)(KB) * (64 + HL_T1_UNITS))      // the one-plane image (hl1_pack_db_kernel)
+// 16-byte unit of plane 0 of (window j, super-row i, elements k .. k + 7) in the image of PL planes (2: h | l; 1: h only);
+// plane p of it is hl_db_plane_units(i) * p further on
+__device__ __forceinline__ int hl_db_plane_units(int i) { return i < 16 ? 64 : HL_T1_UNITS; }
+template <int PL>
+__device__ __forceinline__ int64_t hl_db_unit(int j, int i, int k, int KB) {
+  const int kb = k / 32, kg = (k & 31) >> 3;
+  const int64_t win = (int64_t)j * (PL == 2 ? HL_WIN_UNITS(KB) : HL1_WIN_UNITS(KB));
+  return i < 16 ? win + (int64_t)kb * PL * 64 + i + 16 * kg
+                : win + (int64_t)KB * PL * 64 + (int64_t)kb * PL * HL_T1_UNITS + 11 * kg + (i - 16);
+}
+// piece id -> (window j, super-row i, first element k) and where its eight features sit in the track [N][T][F]: super-row i
+// = frames step * i + tap_stride * {0, 1, 2}; frames beyond the track (in_track false) are zero pieces
+struct HlDbPiece {
+  int j, i, k;
+  int64_t src;             // element offset of the eight features in the track
+  bool in_track;
+};
+__device__ __forceinline__ HlDbPiece hl_db_piece(int64_t id, int T, int F, int step, int tap_stride) {
+  const int K8 = HL_SUB * F / 8;
+  HlDbPiece d;
+  const int k8 = (int)(id % K8);
+  d.i = (int)((id / K8) % HL_ROWS);
+  d.j = (int)(id / ((int64_t)K8 * HL_ROWS));
+  d.k = k8 * 8;
+  const int sub = d.k / F, f = d.k - sub * F;
+  const int t = step * d.i + tap_stride * sub;
+  d.in_track = t < T;
+  d.src = ((int64_t)d.j * T + t) * F + f;
+  return d;
+}
+
 __global__ __launch_bounds__(256) void hl_pack_db_kernel(const float* __restrict__ base, int N, int T, int F, int step,
                                                          int tap_stride, const int32_t* __restrict__ meta,
                                                          _Float16* __restrict__ image) {
@@ -145,51 +237,27 @@ __global__ __launch_bounds__(256) void hl_pack_db_kernel(const float* __restrict
   const int64_t n = (int64_t)N * HL_ROWS * K8;
   const float sc = ldexpf(1.0f, meta[0]);
   for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (int64_t)gridDim.x * blockDim.x) {
-    const int k8 = (int)(id % K8);
-    const int i = (int)((id / K8) % HL_ROWS);
-    const int j = (int)(id / ((int64_t)K8 * HL_ROWS));
-    const int k = k8 * 8, sub = k / F, f = k - sub * F;
-    const int t = step * i + tap_stride * sub;
+    const HlDbPiece d = hl_db_piece(id, T, F, step, tap_stride);
     f32x4 v0 = (f32x4){0.f, 0.f, 0.f, 0.f}, v1 = v0;
-    if (i < HL_ROWS && t < T) {
-      const f32x4* p = reinterpret_cast<const f32x4*>(base + ((int64_t)j * T + t) * F + f);
+    if (d.in_track) {
+      const f32x4* p = reinterpret_cast<const f32x4*>(base + d.src);
       v0 = p[0];
       v1 = p[1];
     }
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 a0, b0, a1, b1;
-      split_hl_audio(v0[e] * sc, a0, b0);
-      split_hl_audio(v1[e] * sc, a1, b1);
-      hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
-    }
-    const int kb = k / 32, kg = (k & 31) >> 3;
-    const int64_t win = (int64_t)j * HL_WIN_UNITS(KB);
-    int64_t u0;
-    int pl;
-    if (i < 16) {
-      pl = 64;
-      u0 = win + (int64_t)kb * 128 + i + 16 * kg;
-    } else {
-      pl = HL_T1_UNITS;
-      u0 = win + (int64_t)KB * 128 + (int64_t)kb * 2 * HL_T1_UNITS + 11 * kg + (i - 16);
-    }
+    hl_split8<true>(v0, v1, sc, hh, ll);
+    const int64_t u0 = hl_db_unit<2>(d.j, d.i, d.k, KB);
     reinterpret_cast<h8*>(image)[u0] = hh;
-    reinterpret_cast<h8*>(image)[u0 + pl] = ll;
+    reinterpret_cast<h8*>(image)[u0 + hl_db_plane_units(d.i)] = ll;
   }
 }
 
 // ---- query image -----------------------------------------------------------------------------------------------------
-// one block per query slot (slots >= Q are written as zeros: chunks are always 48 wide).
-// image[((((chunk*KB + kb)*6 + ct)*2 + plane)*64 + lane][8], ct = half*3 + (q%48)/16, lane = q%16 + 16*((k%32)/8),
-// element k of half `half` = q32[q][half*3F + k].  qexp[q] = the query's scale exponent.
+// one block per query slot (layout: hl_store_col_piece).  qexp[q] = the query's scale exponent.
 __global__ __launch_bounds__(768) void hl_pack_queries_kernel(const float* __restrict__ q32, int Q, int F,
                                                               _Float16* __restrict__ image, int32_t* __restrict__ qexp) {
   const int q = blockIdx.x, tid = threadIdx.x;
   const int D = 2 * HL_SUB * F, KB = HL_SUB * F / 32, K8h = HL_SUB * F / 8;      // K8h 8-element groups per half
-  __shared__ float red[12];
-  __shared__ int e_s;
   float m = 0.f;
   const bool live = q < Q;
   const float* row = q32 + (int64_t)q * D;
@@ -198,17 +266,9 @@ __global__ __launch_bounds__(768) void hl_pack_queries_kernel(const float* __res
       const f32x4 v = reinterpret_cast<const f32x4*>(row)[i];
       m = fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, red[i]);
-    e_s = hl_exponent(m);
-    if (live) qexp[q] = e_s;
-  }
-  __syncthreads();
-  const float sc = ldexpf(1.0f, e_s);
-  const int chunk = q / HL_QC, qq = q % HL_QC;
+  const int e_q = hl_block_exponent<12>(m);
+  if (live && tid == 0) qexp[q] = e_q;
+  const float sc = ldexpf(1.0f, e_q);
   for (int id = tid; id < 2 * K8h; id += blockDim.x) {
     const int half = id / K8h, k8 = id - half * K8h, k = k8 * 8;
     f32x4 v0 = (f32x4){0.f, 0.f, 0.f, 0.f}, v1 = v0;
@@ -218,17 +278,8 @@ __global__ __launch_bounds__(768) void hl_pack_queries_kernel(const float* __res
       v1 = p[1];
     }
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 a0, b0, a1, b1;
-      split_hl_audio(v0[e] * sc, a0, b0);
-      split_hl_audio(v1[e] * sc, a1, b1);
-      hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
-    }
-    const int kb = k / 32, ct = half * 3 + qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
-    const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
-    reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
-    reinterpret_cast<h8*>(image)[(piece + 1) * 64 + lane] = ll;
+    hl_split8<true>(v0, v1, sc, hh, ll);
+    hl_store_col_piece(image, q, HL_QC, KB, k, half * 3, hh, ll);
   }
 }
 
@@ -241,9 +292,7 @@ __device__ __forceinline__ void hl_pack_query_block(int q, int tid, const float*
                                                     double* __restrict__ qn2, _Float16* __restrict__ image,
                                                     int32_t* __restrict__ qexp) {
   const int D = 2 * HL_SUB * F, KB = HL_SUB * F / 32, K8h = HL_SUB * F / 8, n8 = 2 * K8h;
-  __shared__ float redm[12];
   __shared__ double reds[12];
-  __shared__ int e_s;
   const bool live = q < Q;
   const int wq = live ? q_win[q] : 0, t0 = live ? q_t[q] : 0;
   constexpr int MAXU = 2;                                   // 8-element groups per thread (n8 <= 768 * MAXU)
@@ -273,46 +322,25 @@ __device__ __forceinline__ void hl_pack_query_block(int q, int tid, const float*
         }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    m = fmaxf(m, __shfl_down(m, o, 64));
-    s += __shfl_down(s, o, 64);
-  }
-  if ((tid & 63) == 0) {
-    redm[tid >> 6] = m;
-    reds[tid >> 6] = s;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < 12; ++i) {
-      m = fmaxf(m, redm[i]);
-      s += reds[i];
-    }
-    e_s = hl_exponent(m);
-    if (live) {
-      qexp[q] = e_s;
-      qn2[q] = s;
-    }
-  }
-  __syncthreads();
-  const float sc = ldexpf(1.0f, e_s);
-  const int chunk = q / HL_QC, qq = q % HL_QC;
+  // the squared norm: lanes by shuffle here, the waves in order by thread 0 below
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  if ((tid & 63) == 0) reds[tid >> 6] = s;
+  const int e_q = hl_block_exponent<12>(m);                 // (its barriers order reds too)
+  if (live && tid == 0) qexp[q] = e_q;
+  const float sc = ldexpf(1.0f, e_q);
 #pragma unroll
   for (int u = 0; u < MAXU; ++u) {
     const int id = tid + u * 768;
     if (id >= n8) continue;
     const int half = id / K8h, k8 = id - half * K8h, k = k8 * 8;
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 a0, b0, a1, b1;
-      split_hl_audio(v[u][0][e] * sc, a0, b0);
-      split_hl_audio(v[u][1][e] * sc, a1, b1);
-      hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
-    }
-    const int kb = k / 32, ct = half * 3 + qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
-    const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
-    reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
-    reinterpret_cast<h8*>(image)[(piece + 1) * 64 + lane] = ll;
+    hl_split8<true>(v[u][0], v[u][1], sc, hh, ll);
+    hl_store_col_piece(image, q, HL_QC, KB, k, half * 3, hh, ll);
+  }
+  // (last: thread 0's chain of additions would hold up its wave's share of the stores above)
+  if (live && tid == 0) {
+    for (int i = 1; i < 12; ++i) s += reds[i];
+    qn2[q] = s;
   }
 }
 
@@ -328,11 +356,12 @@ __global__ __launch_bounds__(768) void hl_pack_queries_fused_kernel(const float*
 
 // ---- one launch for a clip's whole query side (round 4): the audio pack above AND the text side's query pack ------------------
 // Blocks [0, n_aud) = hl_pack_query_block; blocks [n_aud, n_aud + text slots) = one text query each: gather
-// clip_context[win][row] (GestureKNN.py:549-551), sklearn's f32 normalisation (bit-exact: the four einsum lane chains of
-// qpg_core.hip's l2_normalize_rows_kernel, run by threads 0..3), the normalised row to qn (the select's exact evaluation
-// reads it) and its split-f16 column image (hl_pack_cols_kernel's).  The text side used to start with two tiny launches
-// of its own; behind a sweep that holds every register of every CU they did not get a wave slot before the sweep was over
-// (the text pack sat 100 us in the queue: profiles/r04_step_timeline_graph*.md), and the whole text chain moved behind it.
+// clip_context[win][row] (GestureKNN.py:549-551), sklearn's f32 normalisation (bit-exact: einsum_norm_f32 of qpg_common.h,
+// the four lane chains of qpg_core.hip's l2_normalize_rows_kernel, run by threads 0..3), the normalised row to qn (the
+// select's exact evaluation reads it) and its split-f16 column image (hl_pack_cols_kernel's).  The text side used to start
+// with two tiny launches of its own; behind a sweep that holds every register of every CU they did not get a wave slot
+// before the sweep was over (the text pack sat 100 us in the queue: profiles/r04_step_timeline_graph*.md), and the whole
+// text chain moved behind it.
 struct ClipPackText {
   const float* ctx;        // [Mt][R][Dt]
   const int32_t* q_win;    // [Qt]
@@ -357,42 +386,12 @@ __global__ __launch_bounds__(768) void hl_pack_clip_kernel(const float* __restri
   const int qi = (int)blockIdx.x - n_aud;
   const int D = tx.Dt;
   extern __shared__ __attribute__((aligned(16))) float rowbuf[];         // [D] the normalised row
-  __shared__ float n_s, red[12];
-  __shared__ int e_s;
+  __shared__ float n_s;
   const bool live = qi < tx.Qt;
   const float* p = live ? tx.ctx + ((int64_t)tx.q_win[qi] * tx.R + tx.q_row[qi]) * D : tx.ctx;
   if (tid < 4) {                                       // the norm, in NumPy einsum's order (lane chains l = 0..3)
-    const int l = tid;
-    float a = 0.f;
-    const int nfull = D >> 4;
-    int g = 0;
-    for (; g + 8 <= nfull; g += 8) {
-      float v[32];
-#pragma unroll
-      for (int jx = 0; jx < 32; ++jx) v[jx] = p[(g + (jx >> 2)) * 16 + (jx & 3) * 4 + l];
-#pragma unroll
-      for (int jx = 0; jx < 8; ++jx) {
-#pragma unroll
-        for (int u = 3; u >= 0; --u) a = f_add(f_mul(v[jx * 4 + u], v[jx * 4 + u]), a);
-      }
-    }
-    for (; g < nfull; ++g) {
-#pragma unroll
-      for (int u = 3; u >= 0; --u) {
-        const float v = p[g * 16 + u * 4 + l];
-        a = f_add(f_mul(v, v), a);
-      }
-    }
-    for (int i = nfull * 16; i < D; i += 4) {
-      const float v = (i + l < D) ? p[i + l] : 0.f;
-      a = f_add(f_mul(v, v), a);
-    }
-    const float o1 = __shfl_xor(a, 1, 64);
-    const float pair = f_add(a, o1);
-    const float o2 = __shfl_xor(pair, 2, 64);
-    float n = f_sqrt(f_add(pair, o2));
-    if (n < 10.f * 1.1920928955078125e-07f) n = 1.f;   // sklearn _handle_zeros_in_scale
-    if (l == 0) n_s = n;
+    const float n = einsum_norm_f32(p, D, tid);
+    if (tid == 0) n_s = n;
   }
   __syncthreads();
   const float n = n_s;
@@ -403,32 +402,15 @@ __global__ __launch_bounds__(768) void hl_pack_clip_kernel(const float* __restri
     if (live) tx.qn[(int64_t)qi * D + e] = v;
     m = fmaxf(m, fabsf(v));
   }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < 12; ++i) m = fmaxf(m, red[i]);
-    e_s = hl_exponent(m);
-    if (live) tx.qexp[qi] = e_s;
-  }
-  __syncthreads();
-  const float sc = ldexpf(1.0f, e_s);
+  const int e_q = hl_block_exponent<12>(m);            // (its barriers order rowbuf too)
+  if (live && tid == 0) tx.qexp[qi] = e_q;
+  const float sc = ldexpf(1.0f, e_q);
   const int KB = D / 32, K8 = D / 8;
-  const int chunk = qi / (16 * HL_CT), qq = qi % (16 * HL_CT);
   for (int k8 = tid; k8 < K8; k8 += 768) {
     const int k = k8 * 8;
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 a0, b0;
-      split_hl(rowbuf[k + e] * sc, a0, b0);
-      hh[e] = a0;
-      ll[e] = b0;
-    }
-    const int kb = k / 32, ct = qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
-    const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
-    reinterpret_cast<h8*>(tx.image)[(piece + 0) * 64 + lane] = hh;
-    reinterpret_cast<h8*>(tx.image)[(piece + 1) * 64 + lane] = ll;
+    hl_split8<false>(rowbuf + k, sc, hh, ll);
+    hl_store_col_piece(tx.image, qi, HL_GQC, KB, k, 0, hh, ll);
   }
 }
 
@@ -711,7 +693,6 @@ __device__ __forceinline__ double fast_rsqrt_f64(double x) {
 // relative to |q||c|: chain sums 13.05 x 2^-24 = 7.8e-7, query representation 2^-23 = 1.2e-7 (+ 1e-8 for its subnormal
 // l), f32-stored matrix 1.2e-7: 1.03e-6 <= QPG_AUDIO_HL_ERR (the select keeps ONE band for both images).
 // The 32 registers the l plane's ring held go into the ring's depth: RS = 4 stages (8 k-blocks) of fragments in flight.
-#define HL1_WIN_UNITS(KB) ((int64_t)(KB) * (64 + HL_T1_UNITS))
 // PL: planes of the database image (2: h | l, f32 track; 1: the f16 track); RS: stages of database fragments in flight
 template <int PL, int RS, bool NT>
 __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a) {
@@ -940,13 +921,51 @@ __global__ __launch_bounds__(64 * H2_W, 2) void audio_cosine_hl2_kernel(HlArgs a
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------
 #define HL_F_MAX (1 << 20)    // feature widths beyond this are refused by the size helpers (their products stay inside int64)
+#define HL_META_BYTES 64      // tail of the database and row images: [0] the image's scale exponent, [4] absmax scratch
 extern "C" int64_t qpg_audio_hl_db_bytes(int N, int F) {            // database image + 64 bytes of metadata
-  return (N <= 0 || F <= 0 || F > HL_F_MAX) ? 0 : (int64_t)N * HL_WIN_UNITS((int64_t)HL_SUB * F / 32) * 16 + 64;
+  return (N <= 0 || F <= 0 || F > HL_F_MAX) ? 0
+                                            : (int64_t)N * HL_WIN_UNITS((int64_t)HL_SUB * F / 32) * 16 + HL_META_BYTES;
 }
+static int32_t* hl_db_meta(const void* image, int N, int F) {
+  return reinterpret_cast<int32_t*>(static_cast<unsigned char*>(const_cast<void*>(image)) +
+                                    (qpg_audio_hl_db_bytes(N, F) - HL_META_BYTES));
+}
+
+// A column image as its users see it: the fragments, the per-query exponents behind them, the chunk count - and the
+// bytes of the whole (what the *_bytes helpers return).  image may be NULL (sizes only).
+struct HlColsView {
+  _Float16* frags;
+  int32_t* qexp;           // [chunks * QC]
+  int chunks;
+  int64_t bytes;
+};
+static HlColsView hl_cols_view_of(const void* image, int Q, int QC, int64_t KB) {
+  HlColsView v;
+  const int64_t chunks = ((int64_t)Q + QC - 1) / QC;
+  const int64_t frag_bytes = chunks * KB * HL_CT * 2 * HL_PIECE;
+  unsigned char* img = static_cast<unsigned char*>(const_cast<void*>(image));
+  v.frags = reinterpret_cast<_Float16*>(img);
+  v.qexp = img ? reinterpret_cast<int32_t*>(img + frag_bytes) : nullptr;
+  v.chunks = (int)chunks;
+  v.bytes = frag_bytes + chunks * QC * 4;
+  return v;
+}
+// the audio query image of Q queries of 6 x F features (chunks of 48), the column image of Q queries of D (chunks of 96)
+static HlColsView hl_audio_query_view(const void* image, int Q, int F) {
+  return hl_cols_view_of(image, Q, HL_QC, (int64_t)HL_SUB * F / 32);
+}
+static HlColsView hl_cols_view(const void* image, int Q, int D) { return hl_cols_view_of(image, Q, HL_GQC, D / 32); }
+
 extern "C" int64_t qpg_audio_hl_query_bytes(int Q, int F) {
-  if (Q <= 0 || F <= 0 || F > HL_F_MAX) return 0;
-  const int64_t chunks = ((int64_t)Q + HL_QC - 1) / HL_QC;
-  return chunks * ((int64_t)HL_SUB * F / 32) * HL_CT * 2 * HL_PIECE + chunks * HL_QC * 4;
+  return (Q <= 0 || F <= 0 || F > HL_F_MAX) ? 0 : hl_audio_query_view(nullptr, Q, F).bytes;
+}
+
+// the ONE exponent of a database / row image: max |x| over x [n] -> meta[0] (meta[4] is the maximum's scratch word)
+static void hl_launch_exponent(hipStream_t st, const float* x, int64_t n, int32_t* meta) {
+  unsigned int* amax = reinterpret_cast<unsigned int*>(meta + 4);
+  hipLaunchKernelGGL(hl_zero_u32_kernel, dim3(1), dim3(1), 0, st, amax);
+  hipLaunchKernelGGL(hl_absmax_kernel, dim3(1024), dim3(1024), 0, st, x, n, amax);
+  hipLaunchKernelGGL(hl_exponent_kernel, dim3(1), dim3(1), 0, st, (const unsigned int*)amax, meta);
 }
 
 static bool hl_grid_ok(int T, int F, int G, int n_taps, int tap_stride, int step) {
@@ -970,15 +989,10 @@ extern "C" int qpg_audio_hl_pack_db(qpg_ctx* ctx, void* stream, const float* bas
                   (reinterpret_cast<uintptr_t>(base) % 16) == 0,
               "%s: image too small or misaligned (qpg_audio_hl_db_bytes)", name);
   hipStream_t st = qpg_stream(stream);
-  unsigned char* img = static_cast<unsigned char*>(image);
-  const int64_t body = qpg_audio_hl_db_bytes(N, F) - 64;
-  int32_t* meta = reinterpret_cast<int32_t*>(img + body);
-  unsigned int* amax = reinterpret_cast<unsigned int*>(meta + 4);
-  hipLaunchKernelGGL(hl_zero_u32_kernel, dim3(1), dim3(1), 0, st, amax);
-  hipLaunchKernelGGL(hl_absmax_kernel, dim3(1024), dim3(1024), 0, st, base, (int64_t)N * T * F, amax);
-  hipLaunchKernelGGL(hl_exponent_kernel, dim3(1), dim3(1), 0, st, (const unsigned int*)amax, meta);
+  int32_t* meta = hl_db_meta(image, N, F);
+  hl_launch_exponent(st, base, (int64_t)N * T * F, meta);
   hipLaunchKernelGGL(hl_pack_db_kernel, dim3(4096), dim3(256), 0, st, base, N, T, F, cand_step, tap_stride,
-                     (const int32_t*)meta, reinterpret_cast<_Float16*>(img));
+                     (const int32_t*)meta, static_cast<_Float16*>(image));
   QPG_LAUNCH_CHECK("hl_pack_db_kernel");
   return QPG_OK;
 }
@@ -990,19 +1004,17 @@ extern "C" int qpg_audio_hl_pack_queries(qpg_ctx* ctx, void* stream, const float
   QPG_REQUIRE(image_bytes >= qpg_audio_hl_query_bytes(Q, F) && (reinterpret_cast<uintptr_t>(image) % 16) == 0 &&
                   (reinterpret_cast<uintptr_t>(q32) % 16) == 0,
               "%s: image too small or misaligned (qpg_audio_hl_query_bytes)", name);
-  const int chunks = (Q + HL_QC - 1) / HL_QC;
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* qexp = reinterpret_cast<int32_t*>(img + (int64_t)chunks * (HL_SUB * F / 32) * HL_CT * 2 * HL_PIECE);
-  hipLaunchKernelGGL(hl_pack_queries_kernel, dim3(chunks * HL_QC), dim3(768), 0, qpg_stream(stream), q32, Q, F,
-                     reinterpret_cast<_Float16*>(img), qexp);
+  const HlColsView qv = hl_audio_query_view(image, Q, F);
+  hipLaunchKernelGGL(hl_pack_queries_kernel, dim3(qv.chunks * HL_QC), dim3(768), 0, qpg_stream(stream), q32, Q, F,
+                     qv.frags, qv.qexp);
   QPG_LAUNCH_CHECK("hl_pack_queries_kernel");
   return QPG_OK;
 }
 
-extern "C" int qpg_audio_pack_queries_hl(qpg_ctx* ctx, void* stream, const float* qbase, int M, int T, int F,
-                                         const int32_t* q_win, const int32_t* q_t, int Q, int n_taps, int tap_stride,
-                                         float* q32, double* qn2, void* image, int64_t image_bytes) {
-  const char* name = "qpg_audio_pack_queries_hl";
+// what qpg_audio_pack_queries_hl and qpg_clip_pack_hl ask of the arguments they share
+static int hl_check_audio_pack(const char* name, qpg_ctx* ctx, const float* qbase, int M, int T, int F, const int32_t* q_win,
+                               const int32_t* q_t, int Q, int n_taps, int tap_stride, float* q32, double* qn2, void* image,
+                               int64_t image_bytes) {
   QPG_REQUIRE(ctx && qbase && q_win && q_t && q32 && qn2 && image && M > 0 && T > 0 && Q > 0 && tap_stride > 0,
               "%s: bad argument", name);
   QPG_REQUIRE(n_taps == 2 * HL_SUB && F > 0 && (F % 32) == 0 && 2 * HL_SUB * F / 8 <= 2 * 768,
@@ -1010,11 +1022,19 @@ extern "C" int qpg_audio_pack_queries_hl(qpg_ctx* ctx, void* stream, const float
   QPG_REQUIRE(image_bytes >= qpg_audio_hl_query_bytes(Q, F) && (reinterpret_cast<uintptr_t>(image) % 16) == 0 &&
                   (reinterpret_cast<uintptr_t>(q32) % 16) == 0 && (reinterpret_cast<uintptr_t>(qbase) % 16) == 0,
               "%s: image too small or misaligned (qpg_audio_hl_query_bytes)", name);
-  const int chunks = (Q + HL_QC - 1) / HL_QC;
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* qexp = reinterpret_cast<int32_t*>(img + (int64_t)chunks * (HL_SUB * F / 32) * HL_CT * 2 * HL_PIECE);
-  hipLaunchKernelGGL(hl_pack_queries_fused_kernel, dim3(chunks * HL_QC), dim3(768), 0, qpg_stream(stream), qbase, M, T, F,
-                     q_win, q_t, Q, tap_stride, q32, qn2, reinterpret_cast<_Float16*>(img), qexp);
+  return QPG_OK;
+}
+
+extern "C" int qpg_audio_pack_queries_hl(qpg_ctx* ctx, void* stream, const float* qbase, int M, int T, int F,
+                                         const int32_t* q_win, const int32_t* q_t, int Q, int n_taps, int tap_stride,
+                                         float* q32, double* qn2, void* image, int64_t image_bytes) {
+  const char* name = "qpg_audio_pack_queries_hl";
+  const int rc = hl_check_audio_pack(name, ctx, qbase, M, T, F, q_win, q_t, Q, n_taps, tap_stride, q32, qn2, image,
+                                     image_bytes);
+  if (rc != QPG_OK) return rc;
+  const HlColsView qv = hl_audio_query_view(image, Q, F);
+  hipLaunchKernelGGL(hl_pack_queries_fused_kernel, dim3(qv.chunks * HL_QC), dim3(768), 0, qpg_stream(stream), qbase, M, T, F,
+                     q_win, q_t, Q, tap_stride, q32, qn2, qv.frags, qv.qexp);
   QPG_LAUNCH_CHECK("hl_pack_queries_fused_kernel");
   return QPG_OK;
 }
@@ -1028,49 +1048,42 @@ extern "C" int qpg_clip_pack_hl(qpg_ctx* ctx, void* stream, const float* qbase, 
                                 int64_t image_bytes, const float* text_ctx, int Mt, int R, int Dt, const int32_t* tq_win,
                                 const int32_t* tq_row, int Qt, float* qn_out, void* cols_image, int64_t cols_bytes) {
   const char* name = "qpg_clip_pack_hl";
-  QPG_REQUIRE(ctx && qbase && q_win && q_t && q32 && qn2 && image && M > 0 && T > 0 && Q > 0 && tap_stride > 0,
-              "%s: bad argument", name);
-  QPG_REQUIRE(n_taps == 2 * HL_SUB && F > 0 && (F % 32) == 0 && 2 * HL_SUB * F / 8 <= 2 * 768,
-              "%s: needs 6 taps, F %% 32 == 0, F <= 2048", name);
-  QPG_REQUIRE(image_bytes >= qpg_audio_hl_query_bytes(Q, F) && (reinterpret_cast<uintptr_t>(image) % 16) == 0 &&
-                  (reinterpret_cast<uintptr_t>(q32) % 16) == 0 && (reinterpret_cast<uintptr_t>(qbase) % 16) == 0,
-              "%s: image too small or misaligned (qpg_audio_hl_query_bytes)", name);
+  const int rc = hl_check_audio_pack(name, ctx, qbase, M, T, F, q_win, q_t, Q, n_taps, tap_stride, q32, qn2, image,
+                                     image_bytes);
+  if (rc != QPG_OK) return rc;
   QPG_REQUIRE(text_ctx && tq_win && tq_row && qn_out && cols_image && Mt > 0 && R > 0 && Qt > 0 && Dt > 0 &&
                   (Dt % 128) == 0 && Dt <= 8192 && cols_bytes >= qpg_hl_cols_bytes(Qt, Dt) &&
                   (reinterpret_cast<uintptr_t>(cols_image) % 16) == 0,
               "%s: bad text-side argument (Dt %% 128 == 0, qpg_hl_cols_bytes)", name);
-  const int chunks = (Q + HL_QC - 1) / HL_QC;
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* qexp = reinterpret_cast<int32_t*>(img + (int64_t)chunks * (HL_SUB * F / 32) * HL_CT * 2 * HL_PIECE);
-  const int tchunks = (Qt + HL_GQC - 1) / HL_GQC;
-  unsigned char* cimg = static_cast<unsigned char*>(cols_image);
+  const HlColsView qv = hl_audio_query_view(image, Q, F), tv = hl_cols_view(cols_image, Qt, Dt);
   ClipPackText tx;
   tx.ctx = text_ctx; tx.q_win = tq_win; tx.q_row = tq_row; tx.R = R; tx.Dt = Dt; tx.Qt = Qt; tx.qn = qn_out;
-  tx.image = reinterpret_cast<_Float16*>(cimg);
-  tx.qexp = reinterpret_cast<int32_t*>(cimg + (int64_t)tchunks * (Dt / 32) * HL_CT * 2 * HL_PIECE);
-  const int n_aud = chunks * HL_QC;
-  hipLaunchKernelGGL(hl_pack_clip_kernel, dim3(n_aud + tchunks * HL_GQC), dim3(768), (size_t)Dt * 4, qpg_stream(stream),
-                     qbase, M, T, F, q_win, q_t, Q, tap_stride, q32, qn2, reinterpret_cast<_Float16*>(img), qexp, n_aud, tx);
+  tx.image = tv.frags;
+  tx.qexp = tv.qexp;
+  const int n_aud = qv.chunks * HL_QC;
+  hipLaunchKernelGGL(hl_pack_clip_kernel, dim3(n_aud + tv.chunks * HL_GQC), dim3(768), (size_t)Dt * 4, qpg_stream(stream),
+                     qbase, M, T, F, q_win, q_t, Q, tap_stride, q32, qn2, qv.frags, qv.qexp, n_aud, tx);
   QPG_LAUNCH_CHECK("hl_pack_clip_kernel");
   return QPG_OK;
 }
 
-extern "C" int qpg_audio_cosine_hl(qpg_ctx* ctx, void* stream, const void* db_image, int N, int F, int G,
-                                   const double* cn2, const void* q_image, const double* qn2, int Q, void* D,
-                                   int d_is_f32, int64_t ldD, int32_t* stats) {
-  const char* name = "qpg_audio_cosine_hl";
+// The sweep behind qpg_audio_cosine_hl (PL = 2) and qpg_audio_cosine_hl1 (PL = 1): checks, HlArgs, grid, launch.  kb_div:
+// what KB must be a multiple of (the k loop's trip).  Only the two-plane image has an exponent word (one plane: exponent 0).
+template <int PL, int RS>
+static int hl_cosine_impl(const char* name, const char* kernel_name, int kb_div, qpg_ctx* ctx, void* stream,
+                          const void* db_image, int N, int F, int G, const double* cn2, const void* q_image,
+                          const double* qn2, int Q, void* D, int d_is_f32, int64_t ldD, int32_t* stats) {
   QPG_REQUIRE(ctx && db_image && cn2 && q_image && qn2 && D, "%s: null pointer", name);
-  QPG_REQUIRE(N > 0 && Q > 0 && G == HL_ROWS - 1 && (F % 32) == 0 && ((HL_SUB * F / 32) % (2 * HL_KS)) == 0 &&
+  QPG_REQUIRE(N > 0 && Q > 0 && G == HL_ROWS - 1 && (F % 32) == 0 && ((HL_SUB * F / 32) % kb_div) == 0 &&
                   ldD >= (int64_t)N * G,
               "%s: bad size", name);
-  const int chunks = (Q + HL_QC - 1) / HL_QC, KB = HL_SUB * F / 32;
+  const HlColsView qv = hl_audio_query_view(q_image, Q, F);
+  const int chunks = qv.chunks, KB = HL_SUB * F / 32;
   HlArgs a;
-  const unsigned char* dbi = static_cast<const unsigned char*>(db_image);
-  const unsigned char* qi = static_cast<const unsigned char*>(q_image);
-  a.db = reinterpret_cast<const _Float16*>(dbi);
-  a.meta = reinterpret_cast<const int32_t*>(dbi + (qpg_audio_hl_db_bytes(N, F) - 64));
-  a.qi = reinterpret_cast<const _Float16*>(qi);
-  a.qexp = reinterpret_cast<const int32_t*>(qi + (int64_t)chunks * KB * HL_CT * 2 * HL_PIECE);
+  a.db = static_cast<const _Float16*>(db_image);
+  a.meta = PL == 2 ? hl_db_meta(db_image, N, F) : nullptr;
+  a.qi = qv.frags;
+  a.qexp = qv.qexp;
   a.cn2 = cn2; a.qn2 = qn2; a.D = D; a.zeros = ctx->zeros; a.ldD = ldD; a.stats = stats; a.N = N; a.j0 = 0; a.G = G; a.Q = Q;
   a.KB = KB; a.d_f32 = d_is_f32; a.tmin = nullptr; a.ldT = 0; a.tmask = nullptr; a.band = 0.f; a.chunks = chunks;
   const int64_t g8 = ((int64_t)N + H2_W - 1) / H2_W;
@@ -1078,17 +1091,24 @@ extern "C" int qpg_audio_cosine_hl(qpg_ctx* ctx, void* stream, const void* db_im
   // one query chunk: the image is read ONCE - non-temporal fragment loads (round 5: the kernel with its matrix work compiled
   // out takes 130 us with plain loads, 113 with these); several chunks re-read the image out of the XCD's L2
   const bool nt = chunks == 1;
-  void (*kern)(HlArgs) = nt ? audio_cosine_hl2_kernel<2, H2_RS2, true> : audio_cosine_hl2_kernel<2, H2_RS2, false>;
+  void (*kern)(HlArgs) = nt ? audio_cosine_hl2_kernel<PL, RS, true> : audio_cosine_hl2_kernel<PL, RS, false>;
   hipLaunchKernelGGL(kern,
                      dim3((unsigned)(((g8 + 7) / 8) * 8 * chunks)), dim3(64 * H2_W), 2 * 2 * HL_CT * 2 * HL_PIECE,
                      qpg_stream(stream), a);
-  QPG_LAUNCH_CHECK("audio_cosine_hl2_kernel");
+  QPG_LAUNCH_CHECK(kernel_name);
   return QPG_OK;
+}
+
+extern "C" int qpg_audio_cosine_hl(qpg_ctx* ctx, void* stream, const void* db_image, int N, int F, int G,
+                                   const double* cn2, const void* q_image, const double* qn2, int Q, void* D,
+                                   int d_is_f32, int64_t ldD, int32_t* stats) {
+  return hl_cosine_impl<2, H2_RS2>("qpg_audio_cosine_hl", "audio_cosine_hl2_kernel", 2 * HL_KS, ctx, stream, db_image, N, F,
+                                   G, cn2, q_image, qn2, Q, D, d_is_f32, ldD, stats);
 }
 
 // ---- the one-plane image of an f16-stored track (round 5; BASELINE.json configs[4] "fp16 features") -------------------------
 // thread <-> (window j, super-row i < 27, k8): one 16-byte piece of the f16 base, copied to its fragment position (the
-// layout of hl_pack_db_kernel without the l planes).  No scaling: the values are the database.
+// layout of hl_pack_db_kernel without the l planes: hl_db_unit<1>).  No scaling: the values are the database.
 #define H1_RS 3               // stages of database fragments in flight (audio_cosine_hl2_kernel<1, H1_RS>)
 #define H1_TRIP 6             // stages per trip of its k loop: KB must be a multiple of 2 * H1_TRIP
 __global__ __launch_bounds__(256) void hl1_pack_db_kernel(const _Float16* __restrict__ base, int N, int T, int F, int step,
@@ -1096,18 +1116,10 @@ __global__ __launch_bounds__(256) void hl1_pack_db_kernel(const _Float16* __rest
   const int KB = HL_SUB * F / 32, K8 = HL_SUB * F / 8;
   const int64_t n = (int64_t)N * HL_ROWS * K8;
   for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (int64_t)gridDim.x * blockDim.x) {
-    const int k8 = (int)(id % K8);
-    const int i = (int)((id / K8) % HL_ROWS);
-    const int j = (int)(id / ((int64_t)K8 * HL_ROWS));
-    const int k = k8 * 8, sub = k / F, f = k - sub * F;
-    const int t = step * i + tap_stride * sub;
+    const HlDbPiece d = hl_db_piece(id, T, F, step, tap_stride);
     h8 v = (h8){0, 0, 0, 0, 0, 0, 0, 0};
-    if (t < T) v = *reinterpret_cast<const h8*>(base + ((int64_t)j * T + t) * F + f);
-    const int kb = k / 32, kg = (k & 31) >> 3;
-    const int64_t win = (int64_t)j * HL1_WIN_UNITS(KB);
-    const int64_t u0 = i < 16 ? win + (int64_t)kb * 64 + i + 16 * kg
-                              : win + (int64_t)KB * 64 + (int64_t)kb * HL_T1_UNITS + 11 * kg + (i - 16);
-    reinterpret_cast<h8*>(image)[u0] = v;
+    if (d.in_track) v = *reinterpret_cast<const h8*>(base + d.src);
+    reinterpret_cast<h8*>(image)[hl_db_unit<1>(d.j, d.i, d.k, KB)] = v;
   }
 }
 
@@ -1144,29 +1156,8 @@ extern "C" int qpg_audio_hl1_pack_db(qpg_ctx* ctx, void* stream, const void* bas
 extern "C" int qpg_audio_cosine_hl1(qpg_ctx* ctx, void* stream, const void* db_image, int N, int F, int G, const double* cn2,
                                     const void* q_image, const double* qn2, int Q, void* D, int d_is_f32, int64_t ldD,
                                     int32_t* stats) {
-  const char* name = "qpg_audio_cosine_hl1";
-  QPG_REQUIRE(ctx && db_image && cn2 && q_image && qn2 && D, "%s: null pointer", name);
-  QPG_REQUIRE(N > 0 && Q > 0 && G == HL_ROWS - 1 && (F % 32) == 0 && ((HL_SUB * F / 32) % (2 * H1_TRIP)) == 0 &&
-                  ldD >= (int64_t)N * G,
-              "%s: bad size", name);
-  const int chunks = (Q + HL_QC - 1) / HL_QC, KB = HL_SUB * F / 32;
-  HlArgs a;
-  const unsigned char* qi = static_cast<const unsigned char*>(q_image);
-  a.db = static_cast<const _Float16*>(db_image);
-  a.meta = nullptr;
-  a.qi = reinterpret_cast<const _Float16*>(qi);
-  a.qexp = reinterpret_cast<const int32_t*>(qi + (int64_t)chunks * KB * HL_CT * 2 * HL_PIECE);
-  a.cn2 = cn2; a.qn2 = qn2; a.D = D; a.zeros = ctx->zeros; a.ldD = ldD; a.stats = stats; a.N = N; a.j0 = 0; a.G = G; a.Q = Q;
-  a.KB = KB; a.d_f32 = d_is_f32; a.tmin = nullptr; a.ldT = 0; a.tmask = nullptr; a.band = 0.f; a.chunks = chunks;
-  const int64_t g8 = ((int64_t)N + H2_W - 1) / H2_W;
-  QPG_REQUIRE(((g8 + 7) / 8) * 8 * chunks < 0x7fffffffll, "%s: too many blocks", name);
-  const bool nt = chunks == 1;                                    // (as the two-plane launch)
-  void (*kern)(HlArgs) = nt ? audio_cosine_hl2_kernel<1, H1_RS, true> : audio_cosine_hl2_kernel<1, H1_RS, false>;
-  hipLaunchKernelGGL(kern,
-                     dim3((unsigned)(((g8 + 7) / 8) * 8 * chunks)), dim3(64 * H2_W), 2 * 2 * HL_CT * 2 * HL_PIECE,
-                     qpg_stream(stream), a);
-  QPG_LAUNCH_CHECK("audio_cosine_hl2_kernel<1>");
-  return QPG_OK;
+  return hl_cosine_impl<1, H1_RS>("qpg_audio_cosine_hl1", "audio_cosine_hl2_kernel<1>", 2 * H1_TRIP, ctx, stream, db_image,
+                                  N, F, G, cn2, q_image, qn2, Q, D, d_is_f32, ldD, stats);
 }
 
 // ---- generic split-f16 distance GEMM (BASELINE.json configs[2]: the prefilter of the exact-f32 cosine family) ----------
@@ -1184,15 +1175,8 @@ __global__ __launch_bounds__(256) void hl_pack_rows_kernel(const float* __restri
     const int64_t j = row >> 5;
     const int k = k8 * 8;
     const f32x4* p = reinterpret_cast<const f32x4*>(x + row * D + k);
-    const f32x4 v0 = p[0], v1 = p[1];
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 a0, b0, a1, b1;
-      split_hl(v0[e] * sc, a0, b0);
-      split_hl(v1[e] * sc, a1, b1);
-      hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
-    }
+    hl_split8<false>(p[0], p[1], sc, hh, ll);
     const int kb = k / 32, lane = (i & 15) + 16 * ((k & 31) >> 3);
     const int64_t piece = ((j * 2 + (i >> 4)) * KB + kb) * 2;
     reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
@@ -1204,8 +1188,6 @@ __global__ __launch_bounds__(256) void hl_pack_cols_kernel(const float* __restri
                                                            _Float16* __restrict__ image, int32_t* __restrict__ qexp) {
   const int qi = blockIdx.x, tid = threadIdx.x;
   const int KB = D / 32, K8 = D / 8;
-  __shared__ float red[4];
-  __shared__ int e_s;
   const bool live = qi < Q;
   const float* row = q + (int64_t)qi * D;
   float m = 0.f;
@@ -1214,17 +1196,9 @@ __global__ __launch_bounds__(256) void hl_pack_cols_kernel(const float* __restri
       const f32x4 v = reinterpret_cast<const f32x4*>(row)[i];
       m = fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, red[i]);
-    e_s = hl_exponent(m);
-    if (live) qexp[qi] = e_s;
-  }
-  __syncthreads();
-  const float sc = ldexpf(1.0f, e_s);
-  const int chunk = qi / HL_GQC, qq = qi % HL_GQC;
+  const int e_q = hl_block_exponent<4>(m);
+  if (live && tid == 0) qexp[qi] = e_q;
+  const float sc = ldexpf(1.0f, e_q);
   for (int k8 = tid; k8 < K8; k8 += blockDim.x) {
     const int k = k8 * 8;
     f32x4 v0 = (f32x4){0.f, 0.f, 0.f, 0.f}, v1 = v0;
@@ -1233,27 +1207,20 @@ __global__ __launch_bounds__(256) void hl_pack_cols_kernel(const float* __restri
       v1 = reinterpret_cast<const f32x4*>(row + k)[1];
     }
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      _Float16 a0, b0, a1, b1;
-      split_hl(v0[e] * sc, a0, b0);
-      split_hl(v1[e] * sc, a1, b1);
-      hh[e] = a0; ll[e] = b0; hh[4 + e] = a1; ll[4 + e] = b1;
-    }
-    const int kb = k / 32, ct = qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
-    const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
-    reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
-    reinterpret_cast<h8*>(image)[(piece + 1) * 64 + lane] = ll;
+    hl_split8<false>(v0, v1, sc, hh, ll);
+    hl_store_col_piece(image, qi, HL_GQC, KB, k, 0, hh, ll);
   }
 }
 
 extern "C" int64_t qpg_hl_rows_bytes(int64_t R, int D) {
-  return (R <= 0 || D <= 0 || D > HL_F_MAX || R > (int64_t(1) << 40)) ? 0 : R * D * 4 + 64;
+  return (R <= 0 || D <= 0 || D > HL_F_MAX || R > (int64_t(1) << 40)) ? 0 : R * D * 4 + HL_META_BYTES;
+}
+static int32_t* hl_rows_meta(const void* image, int64_t R, int D) {
+  return reinterpret_cast<int32_t*>(static_cast<unsigned char*>(const_cast<void*>(image)) +
+                                    (qpg_hl_rows_bytes(R, D) - HL_META_BYTES));
 }
 extern "C" int64_t qpg_hl_cols_bytes(int Q, int D) {
-  if (Q <= 0 || D <= 0 || D > HL_F_MAX) return 0;
-  const int64_t chunks = ((int64_t)Q + HL_GQC - 1) / HL_GQC;
-  return chunks * (D / 32) * HL_CT * 2 * HL_PIECE + chunks * HL_GQC * 4;
+  return (Q <= 0 || D <= 0 || D > HL_F_MAX) ? 0 : hl_cols_view(nullptr, Q, D).bytes;
 }
 
 extern "C" int qpg_hl_pack_rows(qpg_ctx* ctx, void* stream, const float* x, int64_t R, int D, void* image,
@@ -1265,14 +1232,10 @@ extern "C" int qpg_hl_pack_rows(qpg_ctx* ctx, void* stream, const float* x, int6
                   (reinterpret_cast<uintptr_t>(x) % 16) == 0,
               "%s: image too small or misaligned (qpg_hl_rows_bytes)", name);
   hipStream_t st = qpg_stream(stream);
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* meta = reinterpret_cast<int32_t*>(img + (qpg_hl_rows_bytes(R, D) - 64));
-  unsigned int* amax = reinterpret_cast<unsigned int*>(meta + 4);
-  hipLaunchKernelGGL(hl_zero_u32_kernel, dim3(1), dim3(1), 0, st, amax);
-  hipLaunchKernelGGL(hl_absmax_kernel, dim3(1024), dim3(1024), 0, st, x, R * D, amax);
-  hipLaunchKernelGGL(hl_exponent_kernel, dim3(1), dim3(1), 0, st, (const unsigned int*)amax, meta);
+  int32_t* meta = hl_rows_meta(image, R, D);
+  hl_launch_exponent(st, x, R * D, meta);
   hipLaunchKernelGGL(hl_pack_rows_kernel, dim3(4096), dim3(256), 0, st, x, R, D, (const int32_t*)meta,
-                     reinterpret_cast<_Float16*>(img));
+                     static_cast<_Float16*>(image));
   QPG_LAUNCH_CHECK("hl_pack_rows_kernel");
   return QPG_OK;
 }
@@ -1283,11 +1246,9 @@ extern "C" int qpg_hl_pack_cols(qpg_ctx* ctx, void* stream, const float* q, int 
   QPG_REQUIRE(image_bytes >= qpg_hl_cols_bytes(Q, D) && (reinterpret_cast<uintptr_t>(image) % 16) == 0 &&
                   (reinterpret_cast<uintptr_t>(q) % 16) == 0,
               "%s: image too small or misaligned (qpg_hl_cols_bytes)", name);
-  const int chunks = (Q + HL_GQC - 1) / HL_GQC;
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* qexp = reinterpret_cast<int32_t*>(img + (int64_t)chunks * (D / 32) * HL_CT * 2 * HL_PIECE);
-  hipLaunchKernelGGL(hl_pack_cols_kernel, dim3(chunks * HL_GQC), dim3(256), 0, qpg_stream(stream), q, Q, D,
-                     reinterpret_cast<_Float16*>(img), qexp);
+  const HlColsView cv = hl_cols_view(image, Q, D);
+  hipLaunchKernelGGL(hl_pack_cols_kernel, dim3(cv.chunks * HL_GQC), dim3(256), 0, qpg_stream(stream), q, Q, D, cv.frags,
+                     cv.qexp);
   QPG_LAUNCH_CHECK("hl_pack_cols_kernel");
   return QPG_OK;
 }
@@ -1296,15 +1257,14 @@ extern "C" int qpg_hl_pack_cols(qpg_ctx* ctx, void* stream, const float* q, int 
 // cfg-3's step spent ~40 of its 300 us in three tiny launches in front of the GEMM - sklearn's normalisation (16 blocks: four
 // lanes per row walking NumPy-einsum's chains), the split-f16 column image, the chain-permuted copy the by-code select reads
 // - and the gaps between them.  One block per query does all three: the norm by four lanes in the reference's order
-// (l2_normalize_rows_kernel's code, bit for bit), the normalised row through LDS, then qn (optional), the column image
-// (hl_pack_cols_kernel's layout and exponent) and the permuted row (perm32_kernel's layout).  Padding queries of the last
-// chunk of 96 write zero fragments, as hl_pack_cols_kernel does.
+// (einsum_norm_f32 of qpg_common.h, which l2_normalize_rows_kernel runs too), the normalised row through LDS, then qn
+// (optional), the column image (hl_pack_cols_kernel's layout and exponent) and the permuted row (perm32_kernel's layout).
+// Padding queries of the last chunk of 96 write zero fragments, as hl_pack_cols_kernel does.
 __global__ __launch_bounds__(128) void hl_prepare_queries_kernel(const float* __restrict__ q, int Q, int D,
                                                                  float* __restrict__ qn, _Float16* __restrict__ image,
                                                                  int32_t* __restrict__ qexp, float* __restrict__ qperm) {
   extern __shared__ __attribute__((aligned(16))) float rowbuf[];         // [D] the raw row, then the normalised row
-  __shared__ float n_s, red[2];
-  __shared__ int e_s;
+  __shared__ float n_s;
   const int qi = blockIdx.x, tid = threadIdx.x;
   const bool live = qi < Q;
   const float* p = q + (int64_t)(live ? qi : 0) * D;
@@ -1313,27 +1273,8 @@ __global__ __launch_bounds__(128) void hl_prepare_queries_kernel(const float* __
   for (int e = tid * 4; e < D; e += 128 * 4) *reinterpret_cast<f32x4*>(rowbuf + e) = *reinterpret_cast<const f32x4*>(p + e);
   __syncthreads();
   if (tid < 4) {                                       // the norm, in NumPy einsum's order (lane chains l = 0..3)
-    const int l = tid;
-    const float* pr = rowbuf;
-    float a = 0.f;
-    const int nfull = D >> 4;
-    for (int g = 0; g < nfull; ++g) {
-#pragma unroll
-      for (int u = 3; u >= 0; --u) {
-        const float v = pr[g * 16 + u * 4 + l];
-        a = f_add(f_mul(v, v), a);
-      }
-    }
-    for (int i = nfull * 16; i < D; i += 4) {
-      const float v = (i + l < D) ? pr[i + l] : 0.f;
-      a = f_add(f_mul(v, v), a);
-    }
-    const float o1 = __shfl_xor(a, 1, 64);
-    const float pair = f_add(a, o1);
-    const float o2 = __shfl_xor(pair, 2, 64);
-    float n = f_sqrt(f_add(pair, o2));
-    if (n < 10.f * 1.1920928955078125e-07f) n = 1.f;   // sklearn _handle_zeros_in_scale
-    if (l == 0) n_s = n;
+    const float n = einsum_norm_f32(rowbuf, D, tid);
+    if (tid == 0) n_s = n;
   }
   __syncthreads();
   const float n = n_s;
@@ -1344,32 +1285,15 @@ __global__ __launch_bounds__(128) void hl_prepare_queries_kernel(const float* __
     if (live && qn) qn[(int64_t)qi * D + e] = v;
     m = fmaxf(m, fabsf(v));
   }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  if (tid == 0) {
-    m = fmaxf(red[0], red[1]);
-    e_s = hl_exponent(m);
-    if (live) qexp[qi] = e_s;
-  }
-  __syncthreads();
-  const float sc = ldexpf(1.0f, e_s);
+  const int e_q = hl_block_exponent<2>(m);             // (its barriers order rowbuf too)
+  if (live && tid == 0) qexp[qi] = e_q;
+  const float sc = ldexpf(1.0f, e_q);
   const int KB = D / 32, K8 = D / 8;
-  const int chunk = qi / HL_GQC, qq = qi % HL_GQC;
   for (int k8 = tid; k8 < K8; k8 += 128) {
     const int k = k8 * 8;
     h8 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 a0, b0;
-      split_hl(rowbuf[k + e] * sc, a0, b0);
-      hh[e] = a0;
-      ll[e] = b0;
-    }
-    const int kb = k / 32, ct = qq / 16, lane = (qq & 15) + 16 * ((k & 31) >> 3);
-    const int64_t piece = ((((int64_t)chunk * KB + kb) * HL_CT + ct) * 2);
-    reinterpret_cast<h8*>(image)[(piece + 0) * 64 + lane] = hh;
-    reinterpret_cast<h8*>(image)[(piece + 1) * 64 + lane] = ll;
+    hl_split8<false>(rowbuf + k, sc, hh, ll);
+    hl_store_col_piece(image, qi, HL_GQC, KB, k, 0, hh, ll);
   }
   if (live && qperm) {
     // y[32 G + 8 k + j] = x[16 (2 G + (j >> 2)) + 4 (3 - (j & 3)) + k]   (perm32_kernel, csrc/qpg_sorted.hip)
@@ -1390,11 +1314,9 @@ extern "C" int qpg_hl_prepare_queries(qpg_ctx* ctx, void* stream, const float* q
                   (reinterpret_cast<uintptr_t>(q) % 16) == 0,
               "%s: image too small or misaligned (qpg_hl_cols_bytes; q and the image 16-byte aligned)", name);
   QPG_REQUIRE(q != qn && q != qperm && (qn == nullptr || qn != qperm), "%s: outputs must not alias the input", name);
-  const int chunks = (Q + HL_GQC - 1) / HL_GQC;
-  unsigned char* img = static_cast<unsigned char*>(image);
-  int32_t* qexp = reinterpret_cast<int32_t*>(img + (int64_t)chunks * (D / 32) * HL_CT * 2 * HL_PIECE);
-  hipLaunchKernelGGL(hl_prepare_queries_kernel, dim3(chunks * HL_GQC), dim3(128), (size_t)D * 4, qpg_stream(stream), q, Q, D,
-                     qn, reinterpret_cast<_Float16*>(img), qexp, qperm);
+  const HlColsView cv = hl_cols_view(image, Q, D);
+  hipLaunchKernelGGL(hl_prepare_queries_kernel, dim3(cv.chunks * HL_GQC), dim3(128), (size_t)D * 4, qpg_stream(stream), q, Q,
+                     D, qn, cv.frags, cv.qexp, qperm);
   QPG_LAUNCH_CHECK("hl_prepare_queries_kernel");
   return QPG_OK;
 }
@@ -1818,6 +1740,21 @@ extern "C" int qpg_debug_gemm64_waves(int nw) {
 }
 #endif
 
+// HlArgs of a generic GEMM: row image x column image -> matrix Dm (may be NULL) and / or tile minima and masks
+static HlArgs hl_gemm_args(qpg_ctx* ctx, const void* rows_image, int64_t R, int D, const void* cols_image, int Q, float* Dm,
+                           int64_t ldD, float* tile_min, int64_t ldT, uint16_t* tile_mask, float band) {
+  const HlColsView cv = hl_cols_view(cols_image, Q, D);
+  HlArgs a;
+  a.db = static_cast<const _Float16*>(rows_image);
+  a.meta = hl_rows_meta(rows_image, R, D);
+  a.qi = cv.frags;
+  a.qexp = cv.qexp;
+  a.cn2 = nullptr; a.qn2 = nullptr; a.D = Dm; a.zeros = ctx->zeros; a.ldD = ldD; a.stats = nullptr;
+  a.N = (int)(R / 32); a.j0 = 0; a.chunks = cv.chunks; a.G = 0; a.Q = Q; a.KB = D / 32; a.d_f32 = 1;
+  a.tmin = tile_min; a.ldT = ldT; a.tmask = tile_mask; a.band = band;
+  return a;
+}
+
 extern "C" int qpg_hl_gemm_tilemin_h(qpg_ctx* ctx, void* stream, const void* rows_image, int64_t R, int D,
                                      const void* cols_image, int Q, float band, float* tile_min, uint16_t* tile_mask,
                                      int64_t ldQ) {
@@ -1825,17 +1762,8 @@ extern "C" int qpg_hl_gemm_tilemin_h(qpg_ctx* ctx, void* stream, const void* row
   QPG_REQUIRE(ctx && rows_image && cols_image && tile_min && tile_mask, "%s: null pointer", name);
   QPG_REQUIRE(R > 0 && (R % 64) == 0 && R / 32 < 0x7fffffff && Q > 0 && D > 0 && (D % 128) == 0 && ldQ >= Q && band >= 0.f,
               "%s: bad size (R %% 64 == 0, D %% 128 == 0, ldQ >= Q, band >= 0)", name);
-  const int chunks = (Q + HL_GQC - 1) / HL_GQC, KB = D / 32;
-  HlArgs a;
-  const unsigned char* ri = static_cast<const unsigned char*>(rows_image);
-  const unsigned char* ci = static_cast<const unsigned char*>(cols_image);
-  a.db = reinterpret_cast<const _Float16*>(ri);
-  a.meta = reinterpret_cast<const int32_t*>(ri + (qpg_hl_rows_bytes(R, D) - 64));
-  a.qi = reinterpret_cast<const _Float16*>(ci);
-  a.qexp = reinterpret_cast<const int32_t*>(ci + (int64_t)chunks * KB * HL_CT * 2 * HL_PIECE);
-  a.cn2 = nullptr; a.qn2 = nullptr; a.D = nullptr; a.zeros = ctx->zeros; a.ldD = 0; a.stats = nullptr;
-  a.N = (int)(R / 32); a.j0 = 0; a.chunks = chunks; a.G = 0; a.Q = Q; a.KB = KB; a.d_f32 = 1; a.tmin = tile_min; a.ldT = ldQ;
-  a.tmask = tile_mask; a.band = band;
+  const HlArgs a = hl_gemm_args(ctx, rows_image, R, D, cols_image, Q, nullptr, 0, tile_min, ldQ, tile_mask, band);
+  const int chunks = a.chunks, KB = a.KB;
   const size_t lds64 = 2 * (size_t)G64_KS * HL_CT * HL_PIECE;         // 48 KB
   static bool raised64 = false;
   if (!raised64) {
@@ -1874,16 +1802,8 @@ static int hl_gemm_impl(const char* name, qpg_ctx* ctx, void* stream, const void
               "%s: bad size (R %% 32 == 0, D %% 128 == 0, ldD %% 4 == 0, 16-byte aligned output)", name);
   QPG_REQUIRE(!tile_min || ldT >= R / 16, "%s: tile_min needs ldT >= R / 16", name);
   QPG_REQUIRE(!tile_mask || (tile_min && band >= 0.f), "%s: tile masks need the tile minima and a band >= 0", name);
-  const int chunks = (Q + HL_GQC - 1) / HL_GQC, KB = D / 32;
-  HlArgs a;
-  const unsigned char* ri = static_cast<const unsigned char*>(rows_image);
-  const unsigned char* ci = static_cast<const unsigned char*>(cols_image);
-  a.db = reinterpret_cast<const _Float16*>(ri);
-  a.meta = reinterpret_cast<const int32_t*>(ri + (qpg_hl_rows_bytes(R, D) - 64));
-  a.qi = reinterpret_cast<const _Float16*>(ci);
-  a.qexp = reinterpret_cast<const int32_t*>(ci + (int64_t)chunks * KB * HL_CT * 2 * HL_PIECE);
-  a.cn2 = nullptr; a.qn2 = nullptr; a.D = Dm; a.zeros = ctx->zeros; a.ldD = ldD; a.stats = nullptr;
-  a.N = (int)(R / 32); a.j0 = 0; a.chunks = chunks; a.G = 0; a.Q = Q; a.KB = KB; a.d_f32 = 1; a.tmin = tile_min; a.ldT = ldT; a.tmask = tile_mask; a.band = band;
+  const HlArgs a = hl_gemm_args(ctx, rows_image, R, D, cols_image, Q, Dm, ldD, tile_min, ldT, tile_mask, band);
+  const int chunks = a.chunks, KB = a.KB;
   // (a clip's 48 text queries stay on the 16-row kernel: it runs UNDER the audio sweep, where the slimmer kernel gets more
   // of the slots the sweep leaves - measured inside the step: 0.273-0.283 ms against 0.281-0.282 with the 32-row kernel,
   // also with three column tiles: experiments/gemm32/README.md)

@@ -67,6 +67,46 @@ __device__ __forceinline__ double f_add(double a, double b) { return a + b; }
 __device__ __forceinline__ double f_sub(double a, double b) { return a - b; }
 __device__ __forceinline__ double f_div(double a, double b) { return a / b; }
 
+// scikit-learn's f32 row norm (normalize(): sqrt(einsum('ij,ij->i', X, X))), bit for bit.  NumPy's einsum keeps 4 lane
+// accumulators (lane = e & 3), visits 16-element groups as u = 3,2,1,0, finishes the tail in 4-wide zero-filled steps and
+// combines (l0+l1)+(l2+l3) - see oracle/knn_oracle.py.  The four lane chains are independent: FOUR ADJACENT LANES of a
+// wave, aligned to 4, call this together with the same row p [D] (global or LDS) and l = 0..3; all four get the norm,
+// _handle_zeros_in_scale's clamp applied (a norm < 10 eps counts as 1: the row is left unscaled).
+__device__ __forceinline__ float einsum_norm_f32(const float* p, int D, int l) {
+  float a = 0.f;
+  const int nfull = D >> 4;
+  int g = 0;
+  // eight 16-element groups per trip: the 32 loads of a lane are in flight together, the additions keep their order
+  // (one group per trip waited a load latency per group: 20 us for 48 rows of 384, the first kernel of a clip's text side)
+  for (; g + 8 <= nfull; g += 8) {
+    float v[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) v[j] = p[(g + (j >> 2)) * 16 + (j & 3) * 4 + l];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+      for (int u = 3; u >= 0; --u) a = f_add(f_mul(v[j * 4 + u], v[j * 4 + u]), a);
+    }
+  }
+  for (; g < nfull; ++g) {
+#pragma unroll
+    for (int u = 3; u >= 0; --u) {
+      const float v = p[g * 16 + u * 4 + l];
+      a = f_add(f_mul(v, v), a);
+    }
+  }
+  for (int i = nfull * 16; i < D; i += 4) {
+    const float v = (i + l < D) ? p[i + l] : 0.f;
+    a = f_add(f_mul(v, v), a);
+  }
+  const float o1 = __shfl_xor(a, 1, 64);
+  const float pair = f_add(a, o1);                    // (l0+l1) on lanes 0,1 ; (l2+l3) on lanes 2,3
+  const float o2 = __shfl_xor(pair, 2, 64);
+  float n = f_sqrt(f_add(pair, o2));                  // IEEE add is commutative: (l0+l1)+(l2+l3) on all 4
+  if (n < 10.f * 1.1920928955078125e-07f) n = 1.f;    // sklearn _handle_zeros_in_scale
+  return n;
+}
+
 // sklearn semantics for degenerate rows: a row whose norm is < 10*eps is left unscaled by
 // normalize(); for an all-zero row that gives 0.5*|other unit vector|^2 = 0.5 (0 if both are zero).
 __device__ __forceinline__ double cosine_from_dot(double dot, double qn2, double cn2) {

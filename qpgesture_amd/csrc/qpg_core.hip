@@ -197,11 +197,9 @@ extern "C" int qpg_audio_cand_norm2(qpg_ctx* ctx, void* stream, const double* fn
 }
 
 // ---------------------------------------------------------------------------------------------
-// scikit-learn-exact float32 row normalisation.  NumPy's einsum keeps 4 lane accumulators
-// (lane = e & 3), visits 16-element groups as u = 3,2,1,0, finishes the tail in 4-wide zero-filled
-// steps and combines (l0+l1)+(l2+l3) — see oracle/knn_oracle.py.  The four lane chains are
-// independent, so a row is handled by 4 adjacent threads (one per einsum lane) and the horizontal
-// sum is two shuffles; every thread then divides its quarter of the row.
+// scikit-learn-exact float32 row normalisation.  The norm is einsum_norm_f32 (qpg_common.h: NumPy
+// einsum's four lane chains), so a row is handled by 4 adjacent threads (one per einsum lane) and
+// the horizontal sum is two shuffles; every thread then divides its quarter of the row.
 // ---------------------------------------------------------------------------------------------
 // GATHER: row r is read from x[(win[r]*R + row[r])*D] (the text queries of a clip: clip_context[int(i/n*30)] of
 // window win[r], GestureKNN.py:549-551) instead of x[r*D].
@@ -216,37 +214,7 @@ __global__ __launch_bounds__(256) void l2_normalize_rows_kernel(const float* __r
   const bool live = r < rows;
   if (!live) r = rows - 1;          // keep the whole aligned group of 4 in the shuffles
   const float* p = GATHER ? x + ((int64_t)win[r] * R + row[r]) * D : x + r * D;
-  float a = 0.f;
-  const int nfull = D >> 4;
-  int g = 0;
-  // eight 16-element groups per trip: the 32 loads of a lane are in flight together, the additions keep their order
-  // (one group per trip waited a load latency per group: 20 us for 48 rows of 384, the first kernel of a clip's text side)
-  for (; g + 8 <= nfull; g += 8) {
-    float v[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) v[j] = p[(g + (j >> 2)) * 16 + (j & 3) * 4 + l];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-      for (int u = 3; u >= 0; --u) a = f_add(f_mul(v[j * 4 + u], v[j * 4 + u]), a);
-    }
-  }
-  for (; g < nfull; ++g) {
-#pragma unroll
-    for (int u = 3; u >= 0; --u) {
-      const float v = p[g * 16 + u * 4 + l];
-      a = f_add(f_mul(v, v), a);
-    }
-  }
-  for (int i = nfull * 16; i < D; i += 4) {
-    const float v = (i + l < D) ? p[i + l] : 0.f;
-    a = f_add(f_mul(v, v), a);
-  }
-  const float o1 = __shfl_xor(a, 1, 64);
-  const float pair = f_add(a, o1);                    // (l0+l1) on lanes 0,1 ; (l2+l3) on lanes 2,3
-  const float o2 = __shfl_xor(pair, 2, 64);
-  float n = f_sqrt(f_add(pair, o2));                  // IEEE add is commutative: (l0+l1)+(l2+l3) on all 4
-  if (n < 10.f * 1.1920928955078125e-07f) n = 1.f;    // sklearn _handle_zeros_in_scale
+  const float n = einsum_norm_f32(p, D, l);
   if (live) {
     float* o = out + r * D;
     int e = l;

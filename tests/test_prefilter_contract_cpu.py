@@ -140,3 +140,55 @@ def test_enough_bits_are_decided_each_way():
         print("PREFILTER-REF %-4s must-set beyond the argmin %.4f  must-clear %.4f" % (setting, beyond, clear))
         assert ((v == 1).sum(axis=1) >= 1).all()              # the argmin itself is always decided
         assert beyond >= 0.01 and clear >= 0.01
+
+
+def test_layout_reference_images_decode_to_their_inputs_and_cover_every_byte_once():
+    """tests/hl_layout_ref.py against itself, on random input with a zero query, one element that sets the exponent and
+    values whose l is an f16 subnormal: read back the way the GEMMs read them (whole fragments, reshaped), the five images
+    hold h = fl16(x 2^e) and an l with x 2^e - h - l (resp. 2^-11 l) within 2^-11 of |x 2^e - h| plus half a subnormal f16
+    step (2^-25; 2^-36 under the 2^-11), zero pieces in the padding slots - and every 16-byte unit of the fragments is
+    written exactly once."""
+    from tests import hl_layout_ref as L
+    rng = np.random.default_rng(11)
+
+    def values(*shape):
+        x = (rng.standard_normal(shape) * np.exp(rng.uniform(np.log(1e-12), 0.0, shape))).astype(np.float32)
+        x.reshape(-1)[rng.integers(0, x.size)] = 300.0                      # sets the exponent
+        return x
+
+    def check(planes, x, e, lscale, tiny):
+        xs = np.asarray(x, np.float32) * np.float32(2.0) ** np.asarray(e, np.float32)
+        h = planes[0].astype(np.float32)
+        assert np.array_equal(planes[0], xs.astype(np.float16))
+        r = (xs - h).astype(np.float64)
+        assert np.all(np.abs(r - planes[1].astype(np.float64) * lscale) <= 2.0 ** -11 * np.abs(r) + tiny)
+        assert np.any((planes[1] != 0) & (np.abs(planes[1].astype(np.float64)) < 2.0 ** -14)), "no subnormal l in the input"
+
+    F, N, T = 128, 3, 157
+    base = values(N, T, F)
+    img = L.db_image(base, 6, 2, 2)
+    assert np.all(img.writes == 1) and img.frags.size == N * (3 * F // 32) * 2 * 108 * 16
+    rows = L.super_rows(base, 6, 2)
+    assert not rows[:, 26, F:].any() and rows[:, 26, :F].any()            # T = 157: frames 158 and 160 lie beyond the track
+    check(L.db_decode(img, N, F, 2), rows, img.exps[0], 1.0, 2.0 ** -25)
+    b16 = base.astype(np.float16)
+    img1 = L.db_image(b16, 6, 2, 1)
+    assert np.all(img1.writes == 1) and img1.exps[0] == 0 and img1.frags.size * 2 == img.frags.size
+    assert np.array_equal(L.db_decode(img1, N, F, 1)[0], L.super_rows(b16, 6, 2))
+
+    for Q, builder, K, halves, qc, lscale, tiny in ((49, L.audio_query_image, 3 * F, 2, L.QC, 1.0, 2.0 ** -25),
+                                                    (97, L.cols_image, 384, 1, L.GQC, 2.0 ** -11, 2.0 ** -36)):
+        q = values(Q, halves * K)
+        q[3] = 0.0
+        img = builder(q)
+        slots = -(-Q // qc) * qc
+        assert np.all(img.writes == 1) and img.frags.size == slots * halves * K * 4 and img.exps.size == slots
+        assert img.exps[3] == 0 and np.all(img.exps[Q:] == 0)
+        planes = L.cols_decode(img, K, halves, qc)
+        assert not planes[:, Q:].any() and not planes[:, 3].any()
+        check(planes[:, :Q], q, img.exps[:Q, None], lscale, tiny)
+
+    x = values(96, 384)
+    img = L.rows_image(x)
+    assert np.all(img.writes == 1) and img.frags.size == x.size * 4
+    check(L.rows_decode(img, 384), x, img.exps[0], 2.0 ** -11, 2.0 ** -36)
