@@ -45,6 +45,25 @@ void qpg_set_error(const char* fmt, ...);
 
 static inline hipStream_t qpg_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Exchange layout of a select's tables (sharded DB): row q lives in block q / q_block of a byte buffer whose blocks are
+// block_stride bytes apart (one block per destination rank, several arrays per block); q_block == 0: plain [Q][K] tables.
+// select_out_rows shifts the two table pointers of query q's block so that out[(int64_t)q * K + k] is its row in either
+// layout; select_block_layout_ok is the entry points' condition (has_rank: a rank / nearest-neighbour output is asked for).
+template <typename T>
+__device__ __forceinline__ void select_out_rows(int q, int K, int q_block, int64_t block_stride,
+                                                T* __restrict__& out_dist, int32_t* __restrict__& out_idx) {
+  if (q_block > 0) {
+    const int64_t shift = (int64_t)(q / q_block) * block_stride;
+    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
+    out_dist = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
+    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
+  }
+}
+static inline bool select_block_layout_ok(int q_block, int64_t block_stride, int Q, bool has_rank) {
+  return q_block >= 0 && (q_block == 0 || (!has_rank && Q % q_block == 0 && block_stride % 8 == 0));
+}
+#define QPG_BLOCK_LAYOUT_MSG "%s: block layout needs Q %% q_block == 0, an 8-byte multiple stride and no rank (or nn) output"
+
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

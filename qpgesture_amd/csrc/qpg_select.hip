@@ -52,14 +52,7 @@ __global__ __launch_bounds__(1024) void percode_select_kernel(const T* __restric
   typedef T vecT __attribute__((ext_vector_type(VEC)));
   typedef int16_t vecC __attribute__((ext_vector_type(VEC)));
   const int q = blockIdx.x;
-  // exchange layout (sharded DB): row q lives in block q / q_block of a byte buffer whose blocks are block_stride
-  // bytes apart (one block per destination rank, several arrays per block); q_block == 0: plain [Q][K] tables
-  if (q_block > 0) {
-    const int64_t shift = (int64_t)(q / q_block) * block_stride;
-    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
-    out_dist = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
-    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
-  }
+  select_out_rows(q, K, q_block, block_stride, out_dist, out_idx);
   const T* row = D + (int64_t)q * ldD;
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
     best[k] = ~0ull;
@@ -195,6 +188,15 @@ struct GuardArgs {
   double eps;
   int32_t* stats;         // [2]
 };
+// An entry point's GuardArgs, and the track geometry all of them need (C < 0: the entry point has no candidate count).
+static int guard_args(const char* name, GuardArgs* A, const float* base, int base_is_f16, const float* q32,
+                      const int32_t* cand_t, int T, int F, int G, int n_taps, int tap_stride, int64_t C, double eps,
+                      int32_t* stats) {
+  QPG_REQUIRE(T > 0 && F > 0 && G > 0 && n_taps > 0 && tap_stride > 0 && (C < 0 || C % G == 0),
+              "%s: bad track geometry (T, F, G, n_taps, tap_stride > 0, C %% G == 0)", name);
+  *A = GuardArgs{base, base_is_f16, q32, cand_t, T, F, G, n_taps, tap_stride, eps, stats};
+  return QPG_OK;
+}
 // Walk-relevance cut of the mixed select's tier-1 lists (round 4; pos_t == nullptr: off).  The walk reads, per step and
 // per previous code p, only the code(s) with the smallest fused score  pos_rank[p][c] + 0.05 freq_rank[c] + rank(c)
 // (GestureKNN.py:540-545, :574-576, order[0] - order[:2] without the text side, :593): a code whose rank is certainly
@@ -263,6 +265,105 @@ __device__ __forceinline__ double refine_pair_f64(const GuardArgs& A, int q, int
   return f_mul(0.5, l == 0 ? f_add(a2, o2) : f_add(o2, a2));
 }
 
+// ---- the pieces every guard shares ------------------------------------------------------------------------------------
+// refine_pair_f64 over a list, one quad per entry: store(i, distance of (q, cand_of(i))) for i in [0, n), `store` on each
+// quad's first lane.  A wave that is wholly past the list skips the evaluation; inside a wave with work the idle quads run
+// along on entry 0 and their value is dropped, so control flow into the quad shuffles stays uniform.  All threads call.
+template <typename CandOf, typename Store>
+__device__ __forceinline__ void refine_list_quads(const GuardArgs& A, int q, int n, CandOf&& cand_of, Store&& store) {
+  const int tid = threadIdx.x;
+  for (int i0 = 0; i0 < n; i0 += blockDim.x / 4) {
+    if (i0 + ((tid >> 6) << 4) >= n) continue;
+    const int i = i0 + (tid >> 2);
+    const double dr = refine_pair_f64(A, q, cand_of(i < n ? i : 0), tid & 3);
+    if (i < n && (tid & 3) == 0) store(i, dr);
+  }
+}
+// The grid-strided form (blocks (x, y) of a (., Y) grid share the n entries of one list): fetch(t, q, c) says whether
+// entry t is live and, if so, names its query and local candidate.  A wave without a live entry skips; idle quads run along
+// on a live lane's pair.
+template <typename Fetch, typename Store>
+__device__ __forceinline__ void refine_list_quads_grid(const GuardArgs& A, int n, Fetch&& fetch, Store&& store) {
+  const int tid = threadIdx.x, per = blockDim.x / 4;
+  for (int t0 = blockIdx.y * per; t0 < n; t0 += gridDim.y * per) {
+    const int t = t0 + (tid >> 2);
+    int q = 0;
+    long long c = 0;
+    const bool live = t < n && fetch(t, q, c);
+    const unsigned long long m = __ballot(live);                      // (wave-uniform: taken before any divergence)
+    if (m == 0) continue;
+    const int src = __ffsll((long long)m) - 1;
+    const int ql = __shfl(q, src, 64);
+    const long long cl = __shfl(c, src, 64);
+    const double dr = refine_pair_f64(A, live ? q : ql, live ? c : cl, tid & 3);
+    if (live && (tid & 3) == 0) store(t, dr);
+  }
+}
+
+// Winner of every code over a list of n (code, distance key, candidate) entries - the reference's strict-`<` scan: the
+// minimum of the ordered keys, a barrier, then the lowest candidate index among the entries equal to it.  code_of(e) < 0:
+// the entry takes no part.  best / besti [K] hold ~0 / 0xffffffff for the codes in play; the caller puts a barrier behind
+// the second sweep.
+template <typename CodeOf, typename KeyOf, typename CandOf>
+__device__ __forceinline__ void list_min_then_first(int n, CodeOf&& code_of, KeyOf&& key_of, CandOf&& cand_of,
+                                                    unsigned long long* best, unsigned int* besti) {
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int k = code_of(e);
+    if (k >= 0) atomicMin(&best[k], (unsigned long long)order_key(key_of(e)));
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int k = code_of(e);
+    if (k >= 0 && (unsigned long long)order_key(key_of(e)) == best[k]) atomicMin(&besti[k], cand_of(e));
+  }
+}
+
+// Minima of DIFFERENT codes closer than eps are neighbours in the sorted order (s_code[r] = code at rank r), so finding
+// them is one look at each rank neighbour, not another K x K sweep: fn(ka, kb) for the present codes at ranks r, r + 1 with
+// v[kb] - v[ka] < eps (absent codes tie at `absent` by design).
+template <typename T, typename Present, typename Fn>
+__device__ __forceinline__ void for_close_rank_neighbours(const int* s_code, const T* v, int K, T eps, Present&& present,
+                                                          Fn&& fn) {
+  for (int r = threadIdx.x; r + 1 < K; r += blockDim.x) {
+    const int ka = s_code[r], kb = s_code[r + 1];
+    if (present(ka) && present(kb) && v[kb] - v[ka] < eps) fn(ka, kb);
+  }
+}
+// The rank-level guard: the codes of every such pair are listed once (claim(k): false for a code whose value already is
+// reference arithmetic or that is listed; list [cap], *n_list == 0 on entry), their winners besti[k] re-evaluated with
+// refine_pair_f64, the values stored to v and the output row, and the row ranked again.  More than `cap` codes: the list is
+// cut and overflow() raises the caller's flag.  All threads call, behind a barrier after the ranking that filled s_code.
+template <typename Present, typename Claim, typename Overflow, typename RankPass>
+__device__ __forceinline__ void settle_rank_ties(const GuardArgs& A, int q, int K, const int* s_code, double* v,
+                                                 const unsigned int* besti, int32_t idx_base, double* out_row, int* list,
+                                                 int cap, int* n_list, Present&& present, Claim&& claim,
+                                                 Overflow&& overflow, RankPass&& rank_pass) {
+  for_close_rank_neighbours(s_code, v, K, A.eps, present, [&](int ka, int kb) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = h ? kb : ka;
+      if (!claim(k)) continue;
+      const int pos = atomicAdd(n_list, 1);
+      if (pos < cap) list[pos] = k;
+    }
+  });
+  __syncthreads();
+  int n = *n_list;
+  if (n == 0) return;
+  if (n > cap) {
+    n = cap;
+    overflow();
+  }
+  refine_list_quads(A, q, n, [&](int i) { return (int64_t)(besti[list[i]] - (unsigned int)idx_base); },
+                    [&](int i, double dr) {
+                      v[list[i]] = dr;
+                      out_row[list[i]] = dr;
+                    });
+  if (threadIdx.x == 0) atomicAdd(&A.stats[0], n);
+  __syncthreads();
+  rank_pass();
+}
+
 __global__ __launch_bounds__(1024) void percode_select_guarded_f64_kernel(
     const double* __restrict__ D, int64_t ldD, const int16_t* __restrict__ cand_code, int64_t C, int K, double absent,
     int32_t idx_base, double* __restrict__ out_dist, int32_t* __restrict__ out_idx, int16_t* __restrict__ out_rank,
@@ -279,12 +380,7 @@ __global__ __launch_bounds__(1024) void percode_select_guarded_f64_kernel(
   int* ctl = l_k + GUARD_LIST;                                                      // [0] list length, [1] any flag
   const int q = blockIdx.x, tid = threadIdx.x;
   const double* row = D + (int64_t)q * ldD;
-  if (q_block > 0) {
-    const int64_t shift = (int64_t)(q / q_block) * block_stride;
-    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
-    out_dist = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
-    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
-  }
+  select_out_rows(q, K, q_block, block_stride, out_dist, out_idx);
   for (int k = tid; k < K; k += blockDim.x) {
     best[k] = ~0ull;
     besti[k] = 0xffffffffu;
@@ -344,22 +440,15 @@ __global__ __launch_bounds__(1024) void percode_select_guarded_f64_kernel(
       n = GUARD_LIST;
       if (tid == 0) A.stats[1] = 1;
     }
-    for (int e0 = 0; e0 < n; e0 += blockDim.x / 4) {
-      const int e = e0 + (tid >> 2);
-      const double dr = refine_pair_f64(A, q, l_c[e < n ? e : 0], tid & 3);
-      if (e < n && (tid & 3) == 0) l_d[e] = dr;
-    }
+    refine_list_quads(A, q, n, [&](int e) { return l_c[e]; }, [&](int e, double dr) { l_d[e] = dr; });
     for (int k = tid; k < K; k += blockDim.x)
       if (near_[k] >= 2) {
         best[k] = ~0ull;
         besti[k] = 0xffffffffu;
       }
     __syncthreads();
-    for (int e = tid; e < n; e += blockDim.x) atomicMin(&best[l_k[e]], (unsigned long long)order_key(l_d[e]));
-    __syncthreads();
-    for (int e = tid; e < n; e += blockDim.x)
-      if ((unsigned long long)order_key(l_d[e]) == best[l_k[e]])
-        atomicMin(&besti[l_k[e]], (unsigned int)(l_c[e] + idx_base));
+    list_min_then_first(n, [&](int e) { return l_k[e]; }, [&](int e) { return l_d[e]; },
+                        [&](int e) { return (unsigned int)(l_c[e] + idx_base); }, best, besti);
     if (tid == 0) atomicAdd(&A.stats[0], n);
     __syncthreads();
   }
@@ -370,8 +459,7 @@ __global__ __launch_bounds__(1024) void percode_select_guarded_f64_kernel(
   if (tid < 2) ctl[tid] = 0;
   __syncthreads();
   // ---- 2. ranks; rank-level near ties: minima of DIFFERENT codes closer than eps are compared in reference
-  // arithmetic.  Two values are that close iff they are neighbours in the sorted order, so the check is one look at
-  // each rank neighbour (the sorted copy is scattered by rank), not another K x K sweep.
+  // arithmetic (settle_rank_ties).
   for (int k = tid; k < K; k += blockDim.x) {
     const bool have = besti[k] != 0xffffffffu;
     out_dist[(int64_t)q * K + k] = v[k];
@@ -392,41 +480,16 @@ __global__ __launch_bounds__(1024) void percode_select_guarded_f64_kernel(
   };
   rank_pass();
   __syncthreads();
-  for (int r = tid; r + 1 < K; r += blockDim.x) {
-    const int ka = s_code[r], kb = s_code[r + 1];
-    if (besti[ka] == 0xffffffffu || besti[kb] == 0xffffffffu) continue;      // absent codes tie at `absent` by design
-    if (v[kb] - v[ka] < A.eps) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = h ? kb : ka;
-        if (near_[k] >= 2) continue;                                          // already a reference-arithmetic value
-        if (atomicExch(&near_[k], 2u) >= 2u) continue;                        // listed once
-        const int pos = atomicAdd(&ctl[0], 1);
-        if (pos < GUARD_LIST) {
-          l_c[pos] = (int)(besti[k] - (unsigned int)idx_base);
-          l_k[pos] = k;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  int n2 = ctl[0];
-  if (n2 == 0) return;
-  if (n2 > GUARD_LIST) {
-    n2 = GUARD_LIST;
-    if (tid == 0) A.stats[1] = 1;
-  }
-  for (int e0 = 0; e0 < n2; e0 += blockDim.x / 4) {
-    const int e = e0 + (tid >> 2);
-    const double dr = refine_pair_f64(A, q, l_c[e < n2 ? e : 0], tid & 3);
-    if (e < n2 && (tid & 3) == 0) {
-      v[l_k[e]] = dr;
-      out_dist[(int64_t)q * K + l_k[e]] = dr;
-    }
-  }
-  if (tid == 0) atomicAdd(&A.stats[0], n2);
-  __syncthreads();
-  rank_pass();
+  settle_rank_ties(
+      A, q, K, s_code, v, besti, idx_base, out_dist + (int64_t)q * K, l_k, GUARD_LIST, &ctl[0],
+      [&](int k) { return besti[k] != 0xffffffffu; },
+      [&](int k) {                                            // already a reference-arithmetic value / listed once
+        return near_[k] < 2 && atomicExch(&near_[k], 2u) < 2u;
+      },
+      [&]() {
+        if (tid == 0) A.stats[1] = 1;
+      },
+      rank_pass);
 }
 
 extern "C" int qpg_percode_select_guarded_f64(qpg_ctx* ctx, void* stream, const double* D, int64_t ldD, int Q,
@@ -435,17 +498,15 @@ extern "C" int qpg_percode_select_guarded_f64(qpg_ctx* ctx, void* stream, const 
                                               int q_block, int64_t block_stride, const float* base, int T, int F,
                                               const int32_t* cand_t, int G, int n_taps, int tap_stride,
                                               const float* q32, double eps, int32_t* stats, int base_is_f16) {
+  const char* name = "qpg_percode_select_guarded_f64";
   QPG_REQUIRE(ctx && D && (cand_code || C == 0) && out_dist && out_idx && base && cand_t && q32 && stats,
-              "qpg_percode_select_guarded_f64: null pointer");
-  QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 2048 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll && T > 0 &&
-                  F > 0 && G > 0 && n_taps > 0 && tap_stride > 0 && eps >= 0.0 && C % G == 0,
-              "qpg_percode_select_guarded_f64: bad size");
-  QPG_REQUIRE(q_block >= 0 && (q_block == 0 || (!out_rank && Q % q_block == 0 && block_stride % 8 == 0)),
-              "qpg_percode_select_guarded_f64: block layout needs Q %% q_block == 0 and no rank output");
-  if (Q == 0) return QPG_OK;
+              "%s: null pointer", name);
+  QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 2048 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll && eps >= 0.0,
+              "%s: bad size (K <= 2048)", name);
+  QPG_REQUIRE(select_block_layout_ok(q_block, block_stride, Q, out_rank), QPG_BLOCK_LAYOUT_MSG, name);
   GuardArgs A;
-  A.base = base; A.half = base_is_f16; A.q32 = q32; A.cand_t = cand_t; A.T = T; A.F = F; A.G = G; A.n_taps = n_taps;
-  A.tap_stride = tap_stride; A.eps = eps; A.stats = stats;
+  if (int rc = guard_args(name, &A, base, base_is_f16, q32, cand_t, T, F, G, n_taps, tap_stride, C, eps, stats)) return rc;
+  if (Q == 0) return QPG_OK;
   size_t sh = 24 * (size_t)K + GUARD_LIST * 16 + 16;
   const int sort_ranks = sh + 12 * (size_t)rank_sort_pow2(K) <= 64 * 1024;          // room for the rank sort's scratch
   if (sort_ranks) sh += 12 * (size_t)rank_sort_pow2(K);
@@ -531,6 +592,22 @@ __device__ __forceinline__ double pair_dot_wave_f64(const GuardArgs& A, int q, i
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   return s;
 }
+// One wave's tier-1 value of (query q, local candidate c): the f64 dot product - `fast`: the WavLM geometry, qrow the
+// query's row (LDS or global) - turned into the cosine distance (qq = |q|^2, cn2 [C] = |c|^2).  LANE 0 returns it (the
+// others 0: the norm is loaded and the division made behind the dot product, on the lane that stores).
+template <int NPER = 4>
+__device__ __forceinline__ double pair_distance_wave(const GuardArgs& A, int q, const float* qrow, int64_t c, int lane,
+                                                     bool fast, double qq, const double* cn2) {
+  const double dot = fast ? pair_dot_fast_f64<NPER>(A, qrow, c, lane) : pair_dot_wave_f64(A, q, c, lane);
+  return lane == 0 ? cosine_from_dot(dot, qq, cn2[c]) : 0.0;
+}
+
+// One field of a workspace layout: `field` = b + o when `bind` (a size-only pass binds nothing), o += bytes.
+template <typename T>
+__host__ __device__ __forceinline__ void ws_field(bool bind, T*& field, unsigned char* b, size_t& o, size_t bytes) {
+  if (bind) field = reinterpret_cast<T*>(b + o);
+  o += bytes;
+}
 
 // Workspace of the cut launch: per query [parking space | streamed state].
 //   parking space   best u64 K | v f64 K | besti u32 K | near u32 K | n, order-valid, pad (16 B) | l_c i32 L | l_k i32 L | l_d f64 L | order i16 K
@@ -596,9 +673,8 @@ __global__ __launch_bounds__(256) void select_refine_kernel(GuardArgs A, int K, 
   const double qq = qn2[q];
   const float* qrow = A.q32 + (int64_t)q * A.n_taps * A.F;
   for (int e = g; e < n; e += ng) {
-    const int c = w_lc[e];
-    const double dot = fast ? pair_dot_fast_f64<NPER>(A, qrow, c, lane) : pair_dot_wave_f64(A, q, c, lane);
-    if (lane == 0) w_ld[e] = cosine_from_dot(dot, qq, cn2[c]);
+    const double d = pair_distance_wave<NPER>(A, q, qrow, w_lc[e], lane, fast != 0, qq, cn2);
+    if (lane == 0) w_ld[e] = d;
   }
 }
 
@@ -726,6 +802,10 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   // phase 1 / 2: the launch is cut at the tier-1 list — phase 1 parks its state in `ws`, select_refine_kernel computes
   // the listed dot products on ALL CUs (a single CU pulls ~26 GB/s; the list of a 48-query clip is ~110 MB of rows),
   // phase 2 picks the state up again.
+  // This kernel writes out what the other selects call by name (list_min_then_first, refine_list_quads,
+  // settle_rank_ties): the hottest select's register allocation moves with each of them (the list launch +1 %, measured),
+  // and with them written out its code is the measured one, instruction for instruction.  A fix to one of those pieces is
+  // made here as well.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned long long* best = reinterpret_cast<unsigned long long*>(smem);               // [K] order key of the minimum
   double* v = reinterpret_cast<double*>(smem + 8 * (size_t)K);                          // [K] value table being ranked
@@ -747,12 +827,8 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
   float* qlds = reinterpret_cast<float*>(pot_k + MIX_POT);   // [n_taps*F] this query's row (fast tier-1 path only)
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nwv = blockDim.x >> 6;
   const DT* row = D + (int64_t)q * ldD;                       // DT = float: the sweep stored its matrix in f32 (half the bytes
-  if (q_block > 0) {                                            // of the two streaming passes, +1.2e-7 inside the bound)
-    const int64_t shift = (int64_t)(q / q_block) * block_stride;
-    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
-    out_dist = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
-    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
-  }
+                                                              // of the two streaming passes, +1.2e-7 inside the bound)
+  select_out_rows(q, K, q_block, block_stride, out_dist, out_idx);
   unsigned char* wq = ws ? mix_query_base(ws, q, K) : nullptr;                // this query's parking space
   for (int k = tid; k < K; k += blockDim.x) {
     best[k] = ~0ull;
@@ -1206,9 +1282,8 @@ __global__ __launch_bounds__(1024) void percode_select_mixed_f64_kernel(
       __syncthreads();
     }
     for (int e = wv; e < n && phase == 0; e += nwv) {
-      const int c = l_c[e];
-      const double dot = fast ? pair_dot_fast_f64<4>(A, qlds, c, lane) : pair_dot_wave_f64(A, q, c, lane);
-      if (lane == 0) l_d[e] = cosine_from_dot(dot, qq, cn2[c]);
+      const double d = pair_distance_wave(A, q, qlds, l_c[e], lane, fast, qq, cn2);
+      if (lane == 0) l_d[e] = d;
     }
     for (int k = tid; k < K; k += blockDim.x)
       if (near_[k] >= 2) {
@@ -1373,16 +1448,13 @@ static int select_mixed_impl(const char* name, qpg_ctx* ctx, void* stream, const
               "%s: null pointer", name);
   QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 512 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll,
               "%s: bad size (K <= 512)", name);
-  QPG_REQUIRE(T > 0 && F > 0 && (F % 4) == 0 && G > 0 && n_taps > 0 && tap_stride > 0 && C % G == 0 &&
-                  eps1 >= 2.0 * QPG_AUDIO_HL_ERR && eps2 >= 0.0 && eps2 < eps1,
+  QPG_REQUIRE((F % 4) == 0 && eps1 >= 2.0 * QPG_AUDIO_HL_ERR && eps2 >= 0.0 && eps2 < eps1,
               "%s: bad geometry (F %% 4 == 0) or eps (eps1 >= 2 x the sweep's error bound - at least %g -, 0 <= eps2 < eps1)",
               name, 2.0 * (double)QPG_AUDIO_HL_ERR);
-  QPG_REQUIRE(q_block >= 0 && (q_block == 0 || (!out_rank && Q % q_block == 0 && block_stride % 8 == 0)),
-              "%s: block layout needs Q %% q_block == 0, an 8-byte multiple stride and no rank output", name);
-  if (Q == 0) return QPG_OK;
+  QPG_REQUIRE(select_block_layout_ok(q_block, block_stride, Q, out_rank), QPG_BLOCK_LAYOUT_MSG, name);
   GuardArgs A;
-  A.base = base; A.half = base_is_f16; A.q32 = q32; A.cand_t = cand_t; A.T = T; A.F = F; A.G = G; A.n_taps = n_taps;
-  A.tap_stride = tap_stride; A.eps = eps2; A.stats = stats;
+  if (int rc = guard_args(name, &A, base, base_is_f16, q32, cand_t, T, F, G, n_taps, tap_stride, C, eps2, stats)) return rc;
+  if (Q == 0) return QPG_OK;
   // fast tier-1 path (WavLM geometry: 6 taps x 1024 features): the query row is staged in LDS (+24 KB: 123 KB in all, one block per CU)
   const int use_qlds = (n_taps == 6 && F == 1024) ? 1 : 0;
   const size_t sh2 = 32 * (size_t)K + 16 * MIX_LIST + 4 * MIX_LIST2 + 32 + 6 * MIX_LIST + 4 * (size_t)K;   // merge phase
@@ -1481,8 +1553,7 @@ static int percode_select(const char* name, qpg_ctx* ctx, void* stream, const T*
   QPG_REQUIRE(ctx && D && (cand_code || C == 0) && out_dist && out_idx, "%s: null pointer", name);
   QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 2048 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll,
               "%s: bad size (K <= 2048, candidate indices must stay below 2^31)", name);
-  QPG_REQUIRE(q_block >= 0 && (q_block == 0 || (!out_rank && Q % q_block == 0 && block_stride % 8 == 0)),
-              "%s: block layout needs Q %% q_block == 0, an 8-byte multiple stride and no rank output", name);
+  QPG_REQUIRE(select_block_layout_ok(q_block, block_stride, Q, out_rank), QPG_BLOCK_LAYOUT_MSG, name);
   if (Q == 0) return QPG_OK;
   const size_t sh = 12 * (size_t)rank_sort_pow2(K) + (size_t)K * sizeof(T);
   hipLaunchKernelGGL((percode_select_kernel<T, KeyT, PACKED>), dim3(Q), dim3(1024), sh, qpg_stream(stream), D, ldD,
@@ -1528,20 +1599,17 @@ struct ExactWs {
   int* cnt;              // [Q] list length
 };
 __host__ static size_t exact_ws_layout(int Q, int64_t C, int K, unsigned char* b, ExactWs* w) {
+  ExactWs e = {};
   size_t o = 0;
   const size_t QK = (size_t)Q * K, QC = (size_t)Q * (size_t)C;
-  if (w) w->wmin = reinterpret_cast<double*>(b + o);
-  o += QK * 8;
-  if (w) w->list_d = reinterpret_cast<double*>(b + o);
-  o += QC * 8;
-  if (w) w->widx = reinterpret_cast<int32_t*>(b + o);
-  o += QK * 4;
-  if (w) w->near_ = reinterpret_cast<unsigned int*>(b + o);
-  o += QK * 4;
-  if (w) w->list_c = reinterpret_cast<int*>(b + o);
-  o += QC * 4;
-  if (w) w->cnt = reinterpret_cast<int*>(b + o);
-  o += ((size_t)Q * 4 + 15) / 16 * 16;
+  const bool bind = w != nullptr;
+  ws_field(bind, e.wmin, b, o, QK * 8);
+  ws_field(bind, e.list_d, b, o, QC * 8);
+  ws_field(bind, e.widx, b, o, QK * 4);
+  ws_field(bind, e.near_, b, o, QK * 4);
+  ws_field(bind, e.list_c, b, o, QC * 4);
+  ws_field(bind, e.cnt, b, o, ((size_t)Q * 4 + 15) / 16 * 16);
+  if (bind) *w = e;
   return o;
 }
 
@@ -1569,20 +1637,15 @@ __global__ __launch_bounds__(256) void exact_band_kernel(const double* __restric
 
 __global__ __launch_bounds__(256) void exact_refine_kernel(GuardArgs A, const int16_t* __restrict__ cand_code, int64_t C,
                                                            int K, ExactWs W) {
-  const int q = blockIdx.x, tid = threadIdx.x;
-  const int n = W.cnt[q];
-  for (int e0 = blockIdx.y * 64; e0 < n; e0 += gridDim.y * 64) {      // 64 quads per block
-    const int e = e0 + (tid >> 2);
-    int c = 0;
-    bool need = false;
-    if (e < n) {
-      c = W.list_c[(int64_t)q * C + e];
-      need = W.near_[(int64_t)q * K + cand_code[c]] >= 2;
-    }
-    if (__ballot(need) == 0ull) continue;                             // wave-uniform: nothing to re-evaluate here
-    const double dr = refine_pair_f64(A, q, need ? c : 0, tid & 3);   // (idle quads run along: uniform control flow)
-    if (need && (tid & 3) == 0) W.list_d[(int64_t)q * C + e] = dr;
-  }
+  const int q = blockIdx.x;
+  refine_list_quads_grid(
+      A, W.cnt[q],
+      [&](int e, int& qe, long long& c) {                             // the members of bands with two or more
+        qe = q;
+        c = W.list_c[(int64_t)q * C + e];
+        return W.near_[(int64_t)q * K + cand_code[c]] >= 2;
+      },
+      [&](int e, double dr) { W.list_d[(int64_t)q * C + e] = dr; });
 }
 
 __global__ __launch_bounds__(1024) void exact_merge_kernel(const int16_t* __restrict__ cand_code, int64_t C, int K,
@@ -1599,12 +1662,7 @@ __global__ __launch_bounds__(1024) void exact_merge_kernel(const int16_t* __rest
   int* l2 = rkc + K;                                                               // [K] rank-level list (codes)
   int* ctl = l2 + K;                                                               // [2]
   const int q = blockIdx.x, tid = threadIdx.x;
-  if (q_block > 0) {
-    const int64_t shift = (int64_t)(q / q_block) * block_stride;
-    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
-    out_dist = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
-    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
-  }
+  select_out_rows(q, K, q_block, block_stride, out_dist, out_idx);
   for (int k = tid; k < K; k += blockDim.x) {
     const unsigned int nr = W.near_[(int64_t)q * K + k];
     const int32_t wi = W.widx[(int64_t)q * K + k];
@@ -1618,21 +1676,17 @@ __global__ __launch_bounds__(1024) void exact_merge_kernel(const int16_t* __rest
   const int n = W.cnt[q];
   const int* lc = W.list_c + (int64_t)q * C;
   const double* ld = W.list_d + (int64_t)q * C;
-  int mine = 0;
-  for (int e = tid; e < n; e += blockDim.x) {
-    const int cd = cand_code[lc[e]];
-    if (nearl[cd] >= 2) {
-      atomicMin(&best[cd], (unsigned long long)order_key(ld[e]));
-      ++mine;
-    }
-  }
-  if (mine) atomicAdd(&ctl[1], mine);
-  __syncthreads();
-  for (int e = tid; e < n; e += blockDim.x) {
-    const int c = lc[e], cd = cand_code[c];
-    if (nearl[cd] >= 2 && (unsigned long long)order_key(ld[e]) == best[cd])
-      atomicMin(&besti[cd], (unsigned int)(c + idx_base));
-  }
+  // re-evaluated pairs (stats[0]): the list entries of the codes with a band.  exact_band_kernel raises near_[code] once
+  // for every entry it lists, so the sum of nearl over those codes equals a count taken entry by entry in the sweep below
+  for (int k = tid; k < K; k += blockDim.x)
+    if (nearl[k] >= 2) atomicAdd(&ctl[1], (int)nearl[k]);
+  list_min_then_first(
+      n,
+      [&](int e) {
+        const int cd = cand_code[lc[e]];
+        return nearl[cd] >= 2 ? cd : -1;
+      },
+      [&](int e) { return ld[e]; }, [&](int e) { return (unsigned int)(lc[e] + idx_base); }, best, besti);
   __syncthreads();
   for (int k = tid; k < K; k += blockDim.x) {
     if (nearl[k] >= 2) v[k] = key_value(best[k], 0.0);
@@ -1650,34 +1704,11 @@ __global__ __launch_bounds__(1024) void exact_merge_kernel(const int16_t* __rest
   };
   rank_pass();
   __syncthreads();
-  for (int r = tid; r + 1 < K; r += blockDim.x) {
-    const int ka = s_code[r], kb = s_code[r + 1];
-    if (besti[ka] == 0xffffffffu || besti[kb] == 0xffffffffu) continue;
-    if (v[kb] - v[ka] < A.eps) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = h ? kb : ka;
-        if (atomicMax(&nearl[k], 2u) >= 2u) continue;                 // a reference-arithmetic value already / listed once
-        l2[atomicAdd(&ctl[0], 1)] = k;                                // at most K entries
-      }
-    }
-  }
-  __syncthreads();
-  const int n2 = ctl[0];
-  if (n2 == 0) return;
-  for (int i0 = 0; i0 < n2; i0 += blockDim.x / 4) {
-    const int i = i0 + (tid >> 2);
-    if (i0 + ((tid >> 6) << 4) >= n2) continue;                       // the whole wave is past the list
-    const int k = l2[i < n2 ? i : 0];
-    const double dr = refine_pair_f64(A, q, (int64_t)(besti[k] - (unsigned int)idx_base), tid & 3);
-    if (i < n2 && (tid & 3) == 0) {
-      v[k] = dr;
-      out_dist[(int64_t)q * K + k] = dr;
-    }
-  }
-  if (tid == 0) atomicAdd(&A.stats[0], n2);
-  __syncthreads();
-  rank_pass();
+  settle_rank_ties(
+      A, q, K, s_code, v, besti, idx_base, out_dist + (int64_t)q * K, l2, K, &ctl[0],   // (at most K entries: no overflow)
+      [&](int k) { return besti[k] != 0xffffffffu; },
+      [&](int k) { return atomicMax(&nearl[k], 2u) < 2u; },           // a reference-arithmetic value already / listed once
+      [&]() {}, rank_pass);
 }
 
 extern "C" int64_t qpg_percode_select_exact_ws_bytes(int Q, int64_t C, int K) {
@@ -1693,19 +1724,16 @@ extern "C" int qpg_percode_select_exact_f64(qpg_ctx* ctx, void* stream, const do
   const char* name = "qpg_percode_select_exact_f64";
   QPG_REQUIRE(ctx && D && (cand_code || C == 0) && out_dist && out_idx && base && cand_t && q32 && stats && ws,
               "%s: null pointer", name);
-  QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 1024 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll && T > 0 &&
-                  F > 0 && G > 0 && n_taps > 0 && tap_stride > 0 && eps >= 0.0 && C % G == 0,
+  QPG_REQUIRE(Q >= 0 && C >= 0 && K > 0 && K <= 1024 && ldD >= C && C + (int64_t)idx_base < 0x7fffffffll && eps >= 0.0,
               "%s: bad size (K <= 1024)", name);
-  QPG_REQUIRE(q_block >= 0 && (q_block == 0 || (!out_rank && Q % q_block == 0 && block_stride % 8 == 0)),
-              "%s: block layout needs Q %% q_block == 0 and no rank output", name);
+  QPG_REQUIRE(select_block_layout_ok(q_block, block_stride, Q, out_rank), QPG_BLOCK_LAYOUT_MSG, name);
+  GuardArgs A;
+  if (int rc = guard_args(name, &A, base, base_is_f16, q32, cand_t, T, F, G, n_taps, tap_stride, C, eps, stats)) return rc;
   QPG_REQUIRE(ws_bytes >= qpg_percode_select_exact_ws_bytes(Q, C, K) && (reinterpret_cast<uintptr_t>(ws) % 16) == 0,
               "%s: workspace too small or misaligned (qpg_percode_select_exact_ws_bytes)", name);
   if (Q == 0) return QPG_OK;
   ExactWs W;
   exact_ws_layout(Q, C, K, static_cast<unsigned char*>(ws), &W);
-  GuardArgs A;
-  A.base = base; A.half = base_is_f16; A.q32 = q32; A.cand_t = cand_t; A.T = T; A.F = F; A.G = G; A.n_taps = n_taps;
-  A.tap_stride = tap_stride; A.eps = eps; A.stats = stats;
   hipStream_t st = qpg_stream(stream);
   const int64_t QK = (int64_t)Q * K;
   hipLaunchKernelGGL(exact_zero_kernel, dim3((unsigned)((QK + 255) / 256)), dim3(256), 0, st, W.near_, QK, W.cnt, Q);
@@ -1791,10 +1819,7 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(const unsigned char*
   // minima of DIFFERENT codes closer than eps2 (rank neighbours): the shards' selects do not compare codes with each
   // other when the ranks are taken after the merge, so this is the only place that sees them
   trouble = 0;
-  for (int r = threadIdx.x; r + 1 < K; r += blockDim.x) {
-    const int ka = s_code[r], kb = s_code[r + 1];
-    trouble |= have[ka] && have[kb] && v[kb] - v[ka] < eps2;
-  }
+  for_close_rank_neighbours(s_code, v, K, eps2, [&](int k) { return have[k] != 0; }, [&](int, int) { trouble = 1; });
   if (trouble) atomicOr(&stats[1], 8);
 }
 
@@ -1945,14 +1970,10 @@ __global__ __launch_bounds__(1024) void merge_mixed_phase1_kernel(
   __syncthreads();
   block_stable_ranks(v, K, rkc, [&](int k, int r) { s_code[r] = k; });
   __syncthreads();
-  for (int r = threadIdx.x; r + 1 < K; r += blockDim.x) {
-    const int ka = s_code[r], kb = s_code[r + 1];
-    if (bi[ka] < 0 || bi[kb] < 0) continue;
-    if (v[kb] - v[ka] < eps1) {
-      flg[ka] = 1;                                               // (benign races: only ever set to 1)
-      flg[kb] = 1;
-    }
-  }
+  for_close_rank_neighbours(s_code, v, K, eps1, [&](int k) { return bi[k] >= 0; }, [&](int ka, int kb) {
+    flg[ka] = 1;                                                 // (benign races: only ever set to 1)
+    flg[kb] = 1;
+  });
   __syncthreads();
   // Slots are DETERMINISTIC (round 4): the request of (query q, code k) to shard w sits at q * Rq + its position among
   // q's requests to w in code order - Rq = R / Q slots per (query, shard), unused ones hold ~0 and the shard skips them.
@@ -2075,8 +2096,8 @@ __global__ __launch_bounds__(256) void shard_refine_kernel(GuardArgs A, const un
     const int q = o * q_stride + (int)(x >> 48);
     const int64_t c = (int64_t)(unsigned int)(x & 0xffffffffu) - cand_base;        // local candidate
     const float* qrow = A.q32 + (int64_t)q * A.n_taps * A.F;
-    const double dot = fast ? pair_dot_fast_f64<4>(A, qrow, c, lane) : pair_dot_wave_f64(A, q, c, lane);
-    if (lane == 0) out[e] = cosine_from_dot(dot, qn2[q], cn2[c]);
+    const double d = pair_distance_wave(A, q, qrow, c, lane, fast != 0, qn2[q], cn2);
+    if (lane == 0) out[e] = d;
   }
 }
 
@@ -2100,37 +2121,26 @@ __global__ __launch_bounds__(1024) void merge_mixed_phase2_kernel(
   }
   __syncthreads();
   const int n = fl_cnt[q];
-  auto entry = [&](int e, int& k, double& d, unsigned int& cand) {
-    const unsigned long long x = fl[(int64_t)q * MM_FL + e];
-    k = (int)(x >> 40);
-    const int w = (int)((x >> 32) & 0xff), j = (int)(x & 0xffffffffu);
-    d = reinterpret_cast<const double*>(resp_recv + (int64_t)w * resp_stride + 8)[j];
-    cand = (unsigned int)reinterpret_cast<const int32_t*>(recv + (int64_t)w * src_stride + idx_off)[(int64_t)q * K + k];
+  // flag-list entry e: code << 40 | shard << 32 | slot of its response
+  auto code_of = [&](int e) { return (int)(fl[(int64_t)q * MM_FL + e] >> 40); };
+  auto shard_of = [&](int e) { return (int64_t)((fl[(int64_t)q * MM_FL + e] >> 32) & 0xff); };
+  auto dist_of = [&](int e) {
+    const int j = (int)(fl[(int64_t)q * MM_FL + e] & 0xffffffffu);
+    return reinterpret_cast<const double*>(resp_recv + shard_of(e) * resp_stride + 8)[j];
+  };
+  auto cand_of = [&](int e) {
+    return (unsigned int)reinterpret_cast<const int32_t*>(recv + shard_of(e) * src_stride + idx_off)[(int64_t)q * K + code_of(e)];
   };
   if (q == 0) {                                          // the response headers' trouble bits (see qpg_flags_stamp)
     int f = 0;
     for (int w = threadIdx.x; w < W; w += blockDim.x) f |= reinterpret_cast<const int32_t*>(resp_recv + (int64_t)w * resp_stride)[1];
     if (f) atomicOr(&stats[1], f);
   }
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    int k;
-    double d;
-    unsigned int c;
-    entry(e, k, d, c);
-    touched[k] = 1;
-    atomicMin(&best[k], (unsigned long long)order_key(d));
-  }
+  for (int e = threadIdx.x; e < n; e += blockDim.x) touched[code_of(e)] = 1;
   __syncthreads();
   for (int k = threadIdx.x; k < K; k += blockDim.x)
     if (touched[k]) besti[k] = 0xffffffffu;
-  __syncthreads();
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    int k;
-    double d;
-    unsigned int c;
-    entry(e, k, d, c);
-    if ((unsigned long long)order_key(d) == best[k]) atomicMin(&besti[k], c);
-  }
+  list_min_then_first(n, code_of, dist_of, cand_of, best, besti);
   __syncthreads();
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
     if (touched[k]) v[k] = key_value(best[k], 0.0);
@@ -2143,13 +2153,8 @@ __global__ __launch_bounds__(1024) void merge_mixed_phase2_kernel(
   // flagged (stats[1] |= 8) and the host re-matches the clip on the path whose responses ARE reference arithmetic.
   int trouble = 0;
   if (eps2 > 0.0)
-    for (int e = threadIdx.x; e < n; e += blockDim.x) {
-      int k;
-      double d;
-      unsigned int c;
-      entry(e, k, d, c);
-      trouble |= c != besti[k] && d <= key_value(best[k], 0.0) + eps2;
-    }
+    for (int e = threadIdx.x; e < n; e += blockDim.x)
+      trouble |= cand_of(e) != besti[code_of(e)] && dist_of(e) <= key_value(best[code_of(e)], 0.0) + eps2;
   if (trouble) atomicOr(&stats[1], 8);
   if (!out_rank) return;
   __syncthreads();
@@ -2162,10 +2167,8 @@ __global__ __launch_bounds__(1024) void merge_mixed_phase2_kernel(
   if (eps2 <= 0.0) return;
   __syncthreads();
   trouble = 0;
-  for (int r = threadIdx.x; r + 1 < K; r += blockDim.x) {
-    const int ka = s_code[r], kb = s_code[r + 1];
-    trouble |= besti[ka] != 0xffffffffu && besti[kb] != 0xffffffffu && v[kb] - v[ka] < eps2;
-  }
+  for_close_rank_neighbours(s_code, v, K, eps2, [&](int k) { return besti[k] != 0xffffffffu; },
+                            [&](int, int) { trouble = 1; });
   if (trouble) atomicOr(&stats[1], 8);
 }
 
@@ -2174,39 +2177,52 @@ __global__ __launch_bounds__(256) void shard_refine_ref_kernel(GuardArgs A, cons
                                                                int64_t req_stride, int R, int q_stride, int64_t cand_base,
                                                                unsigned char* __restrict__ resp, int64_t resp_stride,
                                                                int W, int32_t* __restrict__ stats, int Rq) {
-  const int o = blockIdx.x, tid = threadIdx.x;
+  const int o = blockIdx.x;
   const unsigned char* blk = req_recv + (int64_t)o * req_stride;
   refine_carry_flags(req_recv, req_stride, W, resp, resp_stride, o, stats);
   const unsigned long long* ent = reinterpret_cast<const unsigned long long*>(blk + 8);
   double* out = reinterpret_cast<double*>(resp + (int64_t)o * resp_stride + 8);
   const int Qn = R / Rq;
-  for (int e0 = blockIdx.y * 64; e0 < R; e0 += gridDim.y * 64) {
-    const int t = e0 + (tid >> 2);                                    // position-major slot order (see shard_refine_kernel)
-    const int e = t < R ? (t % Qn) * Rq + t / Qn : 0;
-    unsigned long long x = ent[e];
-    const bool live = t < R && x != ~0ull;
-    // (a wave whose 16 slots are all unused skips the evaluation; otherwise idle quads run along on slot data that is
-    // valid for SOME request - uniform control flow inside refine_pair_f64's quad shuffles)
-    const unsigned long long m = __ballot(live);                      // (wave-uniform: taken before any divergence)
-    if (m == 0) continue;
-    const unsigned long long xl = __shfl(x, __ffsll((long long)m) - 1, 64);   // a live lane's request
-    if (!live) x = xl;
-    const int q = o * q_stride + (int)(x >> 48);
-    const int64_t c = (int64_t)(unsigned int)(x & 0xffffffffu) - cand_base;
-    const double dr = refine_pair_f64(A, q, c, tid & 3);
-    if (live && (tid & 3) == 0) out[e] = dr;
-  }
+  auto slot = [&](int t) { return (t % Qn) * Rq + t / Qn; };          // position-major slot order (see shard_refine_kernel)
+  refine_list_quads_grid(
+      A, R,
+      [&](int t, int& q, long long& c) {
+        const unsigned long long x = ent[slot(t)];
+        q = o * q_stride + (int)(x >> 48);
+        c = (long long)(unsigned int)(x & 0xffffffffu) - cand_base;
+        return x != ~0ull;                                            // (unused slots hold ~0)
+      },
+      [&](int t, double dr) { out[slot(t)] = dr; });
 }
 
-extern "C" int64_t qpg_merge_mixed_ws_bytes(int Q, int K, int fl_cap) {          // prov_d | prov_i | fl | fl_cnt
-  return (Q <= 0 || K <= 0 || fl_cap <= 0) ? 0 : (int64_t)Q * K * 12 + (int64_t)Q * fl_cap * 8 + (int64_t)Q * 4 + 64;
+struct MergeMixedWs {     // what phase 1 of the cross-shard merge leaves for phase 2
+  double* prov_d;         // [Q][K] merged approximate minimum
+  int32_t* prov_i;        // [Q][K] its candidate (then 4 bytes of padding when Q K is odd: fl is 8-byte aligned)
+  unsigned long long* fl; // [Q][fl_cap] flag list
+  int32_t* fl_cnt;        // [Q] its length
+};
+static size_t merge_mixed_ws_layout(int Q, int K, int fl_cap, unsigned char* b, MergeMixedWs* w) {
+  MergeMixedWs m = {};
+  size_t o = 0;
+  const size_t QK = (size_t)Q * K;
+  const bool bind = w != nullptr;
+  ws_field(bind, m.prov_d, b, o, QK * 8);
+  ws_field(bind, m.prov_i, b, o, (QK * 4 + 7) / 8 * 8);
+  ws_field(bind, m.fl, b, o, (size_t)Q * fl_cap * 8);
+  ws_field(bind, m.fl_cnt, b, o, (size_t)Q * 4);
+  if (bind) *w = m;
+  return o;
+}
+// (the layout + 64 bytes of slack, less the padding in front of `fl`: the value this function has returned from the start)
+extern "C" int64_t qpg_merge_mixed_ws_bytes(int Q, int K, int fl_cap) {
+  if (Q <= 0 || K <= 0 || fl_cap <= 0) return 0;
+  return (int64_t)(merge_mixed_ws_layout(Q, K, fl_cap, nullptr, nullptr) + 64 - ((size_t)Q * K * 4) % 8);
 }
 
 extern "C" int qpg_merge_mixed_phase1_f64(qpg_ctx* ctx, void* stream, const void* recv, int W, int64_t src_stride,
                                           int64_t dist_off, int64_t idx_off, int Q, int K, double absent, double eps1,
                                           int R, void* req, int64_t req_stride, void* ws, int64_t ws_bytes,
                                           int32_t* stats, int fl_cap, int64_t flag_off) {
-  const int MM_FL = fl_cap;
   const char* name = "qpg_merge_mixed_phase1_f64";
   QPG_REQUIRE(ctx && recv && req && ws && stats, "%s: null pointer", name);
   QPG_REQUIRE(Q == 0 || (R % Q) == 0, "%s: R must be a multiple of Q (R / Q slots per query and shard)", name);
@@ -2217,11 +2233,8 @@ extern "C" int qpg_merge_mixed_phase1_f64(qpg_ctx* ctx, void* stream, const void
                   (reinterpret_cast<uintptr_t>(ws) % 8) == 0 && (reinterpret_cast<uintptr_t>(req) % 8) == 0,
               "%s: bad size / alignment (W <= 255, Q < 65536, K <= 2048, eps1 > 0)", name);
   if (Q == 0) return QPG_OK;
-  unsigned char* w = static_cast<unsigned char*>(ws);
-  double* prov_d = reinterpret_cast<double*>(w);
-  int32_t* prov_i = reinterpret_cast<int32_t*>(w + (size_t)Q * K * 8);
-  unsigned long long* fl = reinterpret_cast<unsigned long long*>(w + (((size_t)Q * K * 12 + 7) / 8) * 8);
-  int32_t* fl_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(fl) + (size_t)Q * MM_FL * 8);
+  MergeMixedWs w;
+  merge_mixed_ws_layout(Q, K, fl_cap, static_cast<unsigned char*>(ws), &w);
   hipLaunchKernelGGL(merge_mixed_prologue_kernel, dim3(1), dim3(256), 0, qpg_stream(stream),
                      static_cast<unsigned char*>(req), req_stride, W, static_cast<const unsigned char*>(recv), src_stride,
                      flag_off, stats);
@@ -2229,7 +2242,7 @@ extern "C" int qpg_merge_mixed_phase1_f64(qpg_ctx* ctx, void* stream, const void
   hipLaunchKernelGGL(merge_mixed_phase1_kernel, dim3(Q), dim3(1024), (size_t)K * 32 + 8,
                      qpg_stream(stream),
                      static_cast<const unsigned char*>(recv), W, src_stride, dist_off, idx_off, K, absent, eps1, R,
-                     static_cast<unsigned char*>(req), req_stride, prov_d, prov_i, fl, fl_cnt, stats, MM_FL);
+                     static_cast<unsigned char*>(req), req_stride, w.prov_d, w.prov_i, w.fl, w.fl_cnt, stats, fl_cap);
   QPG_LAUNCH_CHECK("merge_mixed_phase1_kernel");
   return QPG_OK;
 }
@@ -2242,12 +2255,11 @@ extern "C" int qpg_shard_refine_f64(qpg_ctx* ctx, void* stream, const void* req_
   const char* name = "qpg_shard_refine_f64";
   QPG_REQUIRE(Rq > 0 && (R % Rq) == 0, "%s: R must be a multiple of Rq (slots per query)", name);
   QPG_REQUIRE(ctx && req_recv && base && cand_t && q32 && qn2 && cn2 && resp, "%s: null pointer", name);
-  QPG_REQUIRE(W > 0 && R > 0 && req_stride >= 8 + 8 * (int64_t)R && resp_stride >= 8 + 8 * (int64_t)R && T > 0 && F > 0 &&
-                  (F % 4) == 0 && G > 0 && n_taps > 0 && tap_stride > 0 && q_stride >= 0,
+  QPG_REQUIRE(W > 0 && R > 0 && req_stride >= 8 + 8 * (int64_t)R && resp_stride >= 8 + 8 * (int64_t)R && (F % 4) == 0 &&
+                  q_stride >= 0,
               "%s: bad size", name);
   GuardArgs A;
-  A.base = base; A.half = base_is_f16; A.q32 = q32; A.cand_t = cand_t; A.T = T; A.F = F; A.G = G; A.n_taps = n_taps;
-  A.tap_stride = tap_stride; A.eps = 0.0; A.stats = nullptr;
+  if (int rc = guard_args(name, &A, base, base_is_f16, q32, cand_t, T, F, G, n_taps, tap_stride, -1, 0.0, nullptr)) return rc;
   if (reference_arithmetic) {
     hipLaunchKernelGGL(shard_refine_ref_kernel, dim3(W, 64), dim3(256), 0, qpg_stream(stream), A,
                        static_cast<const unsigned char*>(req_recv), req_stride, R, q_stride, cand_base,
@@ -2271,21 +2283,17 @@ extern "C" int qpg_merge_mixed_phase2_f64(qpg_ctx* ctx, void* stream, const void
                                           int64_t idx_off, int Q, int K, double absent, const void* ws, int64_t ws_bytes,
                                           const void* resp_recv, int64_t resp_stride, double* out_dist, int32_t* out_idx,
                                           int16_t* out_rank, int32_t* stats, int fl_cap, double eps2) {
-  const int MM_FL = fl_cap;
   const char* name = "qpg_merge_mixed_phase2_f64";
   QPG_REQUIRE(ctx && recv && ws && resp_recv && out_dist && out_idx && stats, "%s: null pointer", name);
   QPG_REQUIRE(W > 0 && Q >= 0 && K > 0 && K <= 2048 && fl_cap > 0 && eps2 >= 0.0 &&
                   ws_bytes >= qpg_merge_mixed_ws_bytes(Q, K, fl_cap) && resp_stride % 8 == 0,
               "%s: bad size", name);
   if (Q == 0) return QPG_OK;
-  const unsigned char* w = static_cast<const unsigned char*>(ws);
-  const double* prov_d = reinterpret_cast<const double*>(w);
-  const int32_t* prov_i = reinterpret_cast<const int32_t*>(w + (size_t)Q * K * 8);
-  const unsigned long long* fl = reinterpret_cast<const unsigned long long*>(w + (((size_t)Q * K * 12 + 7) / 8) * 8);
-  const int32_t* fl_cnt = reinterpret_cast<const int32_t*>(reinterpret_cast<const unsigned char*>(fl) + (size_t)Q * MM_FL * 8);
+  MergeMixedWs w;          // (phase 2 only reads what phase 1 left: the kernel takes these fields as const pointers)
+  merge_mixed_ws_layout(Q, K, fl_cap, static_cast<unsigned char*>(const_cast<void*>(ws)), &w);
   hipLaunchKernelGGL(merge_mixed_phase2_kernel, dim3(Q), dim3(1024), (size_t)K * 24, qpg_stream(stream),
-                     static_cast<const unsigned char*>(recv), W, src_stride, idx_off, K, absent, prov_d, prov_i, fl, fl_cnt,
-                     static_cast<const unsigned char*>(resp_recv), resp_stride, out_dist, out_idx, out_rank, stats, MM_FL,
+                     static_cast<const unsigned char*>(recv), W, src_stride, idx_off, K, absent, w.prov_d, w.prov_i, w.fl, w.fl_cnt,
+                     static_cast<const unsigned char*>(resp_recv), resp_stride, out_dist, out_idx, out_rank, stats, fl_cap,
                      eps2);
   QPG_LAUNCH_CHECK("merge_mixed_phase2_kernel");
   return QPG_OK;

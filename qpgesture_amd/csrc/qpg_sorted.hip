@@ -168,14 +168,9 @@ __global__ __launch_bounds__(SORT_THREADS) void percode_select_sorted_kernel(
     atomicMin(&ebest[cd - k0], ((unsigned long long)okey32(dist) << 32) | (unsigned int)oi);
   }
   __syncthreads();
-  // (4) this range's part of the tables.  Exchange layout (sharded DB): row q lives in block q / q_block of a byte buffer
-  // whose blocks are block_stride bytes apart (qpg_percode_select_f32's); indices leave as global candidate indices.
-  if (q_block > 0) {
-    const int64_t shift = (int64_t)(q / q_block) * block_stride;
-    const int64_t rowoff = (int64_t)(q % q_block) * K - (int64_t)q * K;
-    out_dist = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(out_dist) + shift) + rowoff;
-    out_idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(out_idx) + shift) + rowoff;
-  }
+  // (4) this range's part of the tables, in the exchange layout when asked (select_out_rows: qpg_percode_select_f32's);
+  // indices leave as global candidate indices.
+  select_out_rows(q, K, q_block, block_stride, out_dist, out_idx);
   for (int k = tid; k < KL; k += blockDim.x) {
     const unsigned long long kv = ebest[k];
     const bool have = kv != ~0ull;
@@ -236,9 +231,7 @@ extern "C" int qpg_percode_select_sorted_f32(qpg_ctx* ctx, void* stream, const f
                   K <= 2048 && K <= 0x1fff && Dd > 0 && (Dd % 16) == 0 && (reinterpret_cast<uintptr_t>(xs) % 16) == 0 &&
                   (reinterpret_cast<uintptr_t>(qn) % 16) == 0,
               "%s: bad size / alignment (R %% 16 == 0, D %% 16 == 0, K <= 2048)", name);
-  QPG_REQUIRE(q_block >= 0 && idx_base >= 0 &&
-                  (q_block == 0 || (!out_rank && !out_nn && Q % q_block == 0 && block_stride % 8 == 0)),
-              "%s: block layout needs Q %% q_block == 0, an 8-byte multiple stride and no rank / nn output", name);
+  QPG_REQUIRE(idx_base >= 0 && select_block_layout_ok(q_block, block_stride, Q, out_rank || out_nn), QPG_BLOCK_LAYOUT_MSG, name);
   if (Q == 0) return QPG_OK;
   const int S = K >= 32 * SORT_SPLIT ? SORT_SPLIT : (K >= 32 ? K / 32 : 1);
   const int KLmax = ((K + S - 1) / S + 4) & ~3;          // (multiple of 4: keeps qrow 16-byte aligned)

@@ -287,6 +287,71 @@ def test_cross_shard_merge_returns_the_exact_tables(W, noise):
     assert np.abs(d.cpu().numpy() - rd)[ri >= 0].max() <= c.E
 
 
+def _f64_select(name, which, D, q_block=0, block_stride=0, out=None, ranks=True):
+    """qpg_percode_select_guarded_f64 / _exact_f64 on the f64 matrix D (device) with eps = 1e-12.  Plain tables are prefilled
+    with sentinels; `out` = (dist, idx) views of an exchange buffer.  -> dist, idx, rank (device tensors), stats (numpy)."""
+    import torch
+    from qpgesture_amd import _lib
+    c, o = _case(name), _operands(name)
+    dev, Q, K, C = o["dev"], c.Q, c.K, o["C"]
+    if out is None:
+        out = (torch.full((Q, K), float("nan"), dtype=torch.float64, device=dev), torch.full((Q, K), -7, dtype=torch.int32, device=dev))
+    rank = torch.full((Q, K), -7, dtype=torch.int16, device=dev) if ranks else None
+    stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+    args = [D, D.stride(0), Q, o["code"], C, K, R.ABSENT, 0, out[0], out[1], rank, q_block, block_stride, o["base"], T, c.F,
+            o["cand_t"], G, R.N_TAPS, R.TAP_STRIDE, o["q32"], 1e-12, stats, o["half"]]
+    if which == "exact":
+        ws = torch.empty((int(_lib.load().qpg_percode_select_exact_ws_bytes(Q, C, K)),), dtype=torch.uint8, device=dev)
+        args += [ws, ws.numel()]
+    _lib.call("qpg_percode_select_%s_f64" % which, dev, *args)
+    torch.cuda.synchronize()
+    return out[0], out[1], rank, stats.cpu().numpy()
+
+
+@pytest.mark.parametrize("name", ["odd", "base", "f16_track", "wavlm_width"])
+def test_guarded_and_exact_selects_settle_ties_like_the_reference(name):
+    """The f64 selects on the exact distances themselves, called directly.  The cases hold bit-identical candidate rows
+    inside one code, in two codes and in an all-zero window, so both guard levels (candidates of a code, minima of rank
+    neighbours) fire; tests/test_select_contract_cpu.py checks that nothing else that matters lies inside the band.  Both
+    must return the reference's winners and ranks, distances within 1e-13, the same tables bit for bit, no overflow - and
+    for `base` the same rows in the exchange layout (16 queries per block, 64 bytes of padding between blocks)."""
+    import torch
+    c = _case(name)
+    D = torch.from_numpy(c.exact).to("cuda:0")
+    rd, ri, rr = c.ref
+    present = ri >= 0
+    got = {}
+    for which in ("guarded", "exact"):
+        dist, idx, rank, stats = _f64_select(name, which, D)
+        got[which] = dist, idx, rank
+        d = dist.cpu().numpy()
+        print("CONTRACT %s %s: %d pairs re-evaluated, worst distance error %.3g" % (which, name, stats[0], np.abs(d - rd)[present].max()))
+        assert np.array_equal(idx.cpu().numpy(), ri)
+        assert np.array_equal(rank.cpu().numpy().astype(np.int64), rr)
+        assert np.abs(d - rd)[present].max() <= 1e-13
+        assert np.array_equal(d[~present], np.full((~present).sum(), R.ABSENT))
+        assert stats[1] == 0 and stats[0] > 0
+    for a, b in zip(got["guarded"], got["exact"]):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+    if name != "base":
+        return
+    qb, K = 16, c.K
+    blk = qb * K * 12                                        # a block: dist f64 [qb][K] | idx i32 [qb][K] | 64 bytes of padding
+    for which in ("guarded", "exact"):
+        # (without a rank output the rank-level guard does not run, so the minima it would have re-evaluated keep the values
+        # they were given: the rows are those of the plain layout WITHOUT ranks - same winners, distances within 1e-13)
+        pd, pi, _, pstats = _f64_select(name, which, D, ranks=False)
+        assert torch.equal(pi, got[which][1]) and np.abs(pd.cpu().numpy() - rd)[present].max() <= 1e-13
+        buf = torch.full(((c.Q // qb) * (blk + 64),), 0x5A, dtype=torch.uint8, device="cuda:0")
+        out = (buf[:qb * K * 8].view(torch.float64), buf[qb * K * 8:blk].view(torch.int32))
+        _, _, _, stats = _f64_select(name, which, D, q_block=qb, block_stride=blk + 64, out=out, ranks=False)
+        assert stats[1] == 0 and stats[0] > 0 and stats[0] == pstats[0]
+        blocks = buf.view(c.Q // qb, blk + 64)
+        assert torch.equal(blocks[:, :qb * K * 8].contiguous().view(-1), pd.view(torch.uint8).view(-1))
+        assert torch.equal(blocks[:, qb * K * 8:blk].contiguous().view(-1), pi.view(torch.uint8).view(-1))
+        assert bool((blocks[:, blk:] == 0x5A).all())
+
+
 # ---- text ------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _text_device():

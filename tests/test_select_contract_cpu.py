@@ -105,6 +105,20 @@ def test_every_gpu_case_is_admissible():
     assert v["ok"], v["why"]
 
 
+@pytest.mark.parametrize("name,listed_max", [("odd", 27), ("base", 46), ("f16_track", 44), ("wavlm_width", 38)])
+def test_f64_select_cases_are_admissible_at_eps_1e_12(name, listed_max):
+    """The condition that keeps the direct test of qpg_percode_select_guarded_f64 / _exact_f64 decisive: handed the exact
+    distances (E = 0) with a band of 1e-12, nothing that matters is closer than 1e-10 unless its rows are identical, at most
+    half of the guarded select's 256-entry list is used, and the band is not empty."""
+    c = R.audio_case(name)
+    v = R.admissible(c.exact, c.cand_code, c.K, 1e-12, 0.0, 1e-12, row_id=c.row_id, capacity=256, min_mean=1)
+    print("%-12s eps=1e-12: admissible=%s; listed max %d (capacity 256), %.1f same-code candidates + %.1f rank-neighbour "
+          "winners per query %s" % (name, v["ok"], v["listed_max"], v["band_members"], v["rank_members"], v["why"]))
+    assert v["ok"], v["why"]
+    assert v["listed_max"] == listed_max
+    assert name == "odd" or v["rank_members"] > 3
+
+
 def test_negative_controls_are_determined_by_their_inputs():
     """A band of 1.05 E under swap noise of amplitude E cannot hold a pair whose exact gap is below 0.95 E (the two arrive
     2 E - gap > 1.05 E apart, reversed): such pairs exist in the cases the GPU negative controls use."""
