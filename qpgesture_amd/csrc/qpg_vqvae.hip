@@ -498,16 +498,6 @@ extern "C" int qpg_vq_gather_f32(qpg_ctx* ctx, void* stream, const float* k, con
 // ---------------------------------------------------------------------------------------------
 // split-K scratch of the whole-network calls: the 4th region of the workspace
 #define VQ_SPLITK_ROWS 2048
-struct SplitWs {
-  float* p;
-  int64_t n;
-};
-static int conv_call(qpg_ctx* ctx, void* stream, const qpg_conv_desc& c, const float* x, int B, int T_in, int in_stride,
-                     int in_offset, int dil, int T_out, int out_stride, int out_offset, int T_y, const float* res,
-                     int relu_in, int relu_out, float* y, SplitWs sw = SplitWs{nullptr, 0}) {
-  return qpg_conv1d_f32(ctx, stream, x, B, T_in, c.cin, c.w, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad, in_stride,
-                        in_offset, dil, T_out, out_stride, out_offset, T_y, res, relu_in, relu_out, y, sw.p, sw.n);
-}
 
 static int ipow(int b, int e) {
   int r = 1;
@@ -520,26 +510,22 @@ static bool model_ok(const qpg_vq_model* m) {
          m->width > 0 && m->emb > 0 && m->bins > 0 && m->in_dim > 0 && m->growth > 0 && m->k && m->kk;
 }
 
-extern "C" int64_t qpg_vq_workspace_floats(const qpg_vq_model* m, int B, int T) {
-  if (!model_ok(m) || B < 0 || T < 0) return -1;
+// The workspace: three activation slabs [B][T][widest layer] (T/2 rows would do for two of them; kept simple), the
+// split-K scratch, 64 floats of slack.  The size query and both walks carve it here.
+struct VqCarve {
+  int64_t slab, total;
+};
+static VqCarve vq_carve(const qpg_vq_model* m, int B, int T) {
   int64_t cmax = m->width > m->emb ? m->width : m->emb;
   if (m->bins > cmax) cmax = m->bins;
   const int64_t cpad = ((cmax + CV_BN - 1) / CV_BN) * CV_BN;
-  return 3 * (((int64_t)B * T * cmax + 3) / 4 * 4) + 8 * (int64_t)VQ_SPLITK_ROWS * cpad + 64;
+  const int64_t slab = ((int64_t)B * T * cmax + 3) / 4 * 4;
+  return VqCarve{slab, 3 * slab + 8 * (int64_t)VQ_SPLITK_ROWS * cpad + 64};
 }
 
-// x + conv1x1(relu(conv3_dil(relu(x)))) for each block; ping-pongs between cur and alt, h is the hidden buffer
-static int resnet_run(qpg_ctx* ctx, void* stream, const qpg_conv_desc (*blocks)[2], int depth, int growth, bool reverse,
-                      int B, int T, float*& cur, float*& alt, float* h, SplitWs sw) {
-  for (int d = 0; d < depth; ++d) {
-    const int dil = ipow(growth, reverse ? depth - 1 - d : d);                       // resnet.py:57-62
-    int rc = conv_call(ctx, stream, blocks[d][0], cur, B, T, 1, -dil, dil, T, 1, 0, T, nullptr, 1, 1, h, sw);
-    if (rc) return rc;
-    rc = conv_call(ctx, stream, blocks[d][1], h, B, T, 1, 0, 1, T, 1, 0, T, cur, 0, 0, alt, sw);
-    if (rc) return rc;
-    float* t = cur; cur = alt; alt = t;
-  }
-  return QPG_OK;
+extern "C" int64_t qpg_vq_workspace_floats(const qpg_vq_model* m, int B, int T) {
+  if (!model_ok(m) || B < 0 || T < 0) return -1;
+  return vq_carve(m, B, T).total;
 }
 
 // ---- transposed-formulation path (csrc/qpg_convt.hip): taken when the descriptor carries the T-packed images ----
@@ -562,71 +548,59 @@ static bool tpath_ok(const qpg_vq_model* m, bool enc) {
   return enc ? (m->enc_out.wt && m->kT.wt) : (m->dec_in.wt && m->dec_out.wt);
 }
 
-static int convt_call(qpg_ctx* ctx, void* stream, const qpg_conv_desc& c, const float* x, int Cx, int B, int T_in,
-                      int in_stride, int in_offset, int dil, int T_out, int out_stride, int out_offset, int T_y,
-                      const float* res, int relu_in, int relu_out, float* y) {
-  return qpg_convt_f32(ctx, stream, x, B, T_in, Cx, c.wt, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad, in_stride,
-                       in_offset, dil, T_out, out_stride, out_offset, T_y, res, relu_in, relu_out, y);
-}
+// One whole-network call: where it launches, on which kernels (tpath: the T-packed images, activations Cin_pad wide;
+// else the LDS-tiled kernel with the split-K scratch) and the carved workspace.  Layers write to alt (or h) and swap.
+struct VqWalk {
+  qpg_ctx* ctx;
+  void* stream;
+  bool tpath;
+  float *cur, *alt, *h, *splitk;
+  int64_t splitk_floats;
 
-// Resnet1D with the fused block kernel where a launch of 64-row tiles fills the chip, the two-launch form below that
-static int resnet_tpath(qpg_ctx* ctx, void* stream, const qpg_conv_desc (*blocks)[2], const float* const* packs, int depth,
-                        int growth, bool reverse, int B, int T, float*& cur, float*& alt, float* h) {
-  const int64_t tiles = ((int64_t)B * T + 63) / 64;
-  const bool fused = tiles * 4 >= (int64_t)ctx->n_cu * 3;
-  for (int d = 0; d < depth; ++d) {
-    const int dil = ipow(growth, reverse ? depth - 1 - d : d);
-    int rc;
-    if (fused) {
-      rc = qpg_resblock_f32(ctx, stream, cur, B, T, dil, packs[d], blocks[d][0].b, blocks[d][1].b, alt, nullptr);
-    } else {
-      rc = convt_call(ctx, stream, blocks[d][0], cur, 512, B, T, 1, -dil, dil, T, 1, 0, T, nullptr, 1, 1, h);
+  VqWalk(qpg_ctx* c, void* s, bool t, const qpg_vq_model* m, int B, int T, float* ws, int64_t ws_floats)
+      : ctx(c), stream(s), tpath(t) {
+    const int64_t slab = vq_carve(m, B, T).slab;
+    cur = ws, alt = ws + slab, h = ws + 2 * slab, splitk = ws + 3 * slab, splitk_floats = ws_floats - 3 * slab;
+  }
+  void swap() { float* t = cur; cur = alt; alt = t; }
+
+  int conv(const qpg_conv_desc& c, const float* x, int B, int T_in, int in_stride, int in_offset, int dil, int T_out,
+           int out_stride, int out_offset, int T_y, const float* res, int relu_in, int relu_out, float* y) const {
+    if (tpath)
+      return qpg_convt_f32(ctx, stream, x, B, T_in, c.cin_pad, c.wt, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad, in_stride,
+                           in_offset, dil, T_out, out_stride, out_offset, T_y, res, relu_in, relu_out, y);
+    return qpg_conv1d_f32(ctx, stream, x, B, T_in, c.cin, c.w, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad, in_stride,
+                          in_offset, dil, T_out, out_stride, out_offset, T_y, res, relu_in, relu_out, y, splitk,
+                          splitk_floats);
+  }
+  // k3 s1 p1 convolution (enc_out, dec_in, dec_out)
+  int conv3(const qpg_conv_desc& c, const float* x, int B, int T, float* y) const {
+    return conv(c, x, B, T, 1, -1, 1, T, 1, 0, T, nullptr, 0, 0, y);
+  }
+
+  // Resnet1D: cur <- cur + conv1x1(relu(conv3_dil(relu(cur)))) per block (dilations resnet.py:57-62).  T path: the
+  // fused block kernel where a launch of 64-row tiles fills the chip, the two-launch form below that.
+  int resnet(const qpg_vq_model* m, const qpg_conv_desc (*blocks)[2], const float* const* packs, bool reverse, int B,
+             int T) {
+    const bool fused = tpath && (((int64_t)B * T + 63) / 64) * 4 >= (int64_t)ctx->n_cu * 3;
+    for (int d = 0; d < m->depth; ++d) {
+      const int dil = ipow(m->growth, reverse ? m->depth - 1 - d : d);
+      int rc;
+      if (fused) {
+        rc = qpg_resblock_f32(ctx, stream, cur, B, T, dil, packs[d], blocks[d][0].b, blocks[d][1].b, alt, nullptr);
+      } else {
+        rc = conv(blocks[d][0], cur, B, T, 1, -dil, dil, T, 1, 0, T, nullptr, 1, 1, h);
+        if (rc) return rc;
+        rc = conv(blocks[d][1], h, B, T, 1, 0, 1, T, 1, 0, T, cur, 0, 0, alt);
+      }
       if (rc) return rc;
-      rc = convt_call(ctx, stream, blocks[d][1], h, 512, B, T, 1, 0, 1, T, 1, 0, T, cur, 0, 0, alt);
+      swap();
     }
-    if (rc) return rc;
-    float* t = cur; cur = alt; alt = t;
+    return QPG_OK;
   }
-  return QPG_OK;
-}
+};
 
-static int encode_tpath(qpg_ctx* ctx, void* stream, const qpg_vq_model* m, const float* x, int B, int T, float* cur,
-                        float* alt, float* h, int64_t* ids, float* latent, float* margin) {
-  // pose rows (135 floats = 540 B) -> 16-byte aligned rows of cin_pad floats
-  const int cp = m->enc_down[0].cin_pad;
-  int rc = qpg_pad_channels_f32(ctx, stream, x, (int64_t)B * T, m->in_dim, cp, h);
-  if (rc) return rc;
-  const float* in = h;
-  int Cx = cp, Tc = T;
-  for (int i = 0; i < m->down_t; ++i) {
-    const int To = Tc / 2;
-    rc = convt_call(ctx, stream, m->enc_down[i], in, Cx, B, Tc, 2, -1, 1, To, 1, 0, To, nullptr, 0, 0, alt);
-    if (rc) return rc;
-    { float* t = cur; cur = alt; alt = t; }
-    Tc = To;
-    rc = resnet_tpath(ctx, stream, m->enc_res[i], m->enc_res_pack[i], m->depth, m->growth, false, B, Tc, cur, alt, h);
-    if (rc) return rc;
-    in = cur;
-    Cx = 512;
-  }
-  float* z = latent ? latent : alt;
-  rc = convt_call(ctx, stream, m->enc_out, cur, 512, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, z);
-  if (rc) return rc;
-  const int64_t R = (int64_t)B * Tc;
-  QPG_REQUIRE(R < 0x7fffffffll, "qpg_vq_encode_f32: too many latent rows");
-  float* dot = h;
-  rc = convt_call(ctx, stream, m->kT, z, 512, 1, (int)R, 1, 0, 1, (int)R, 1, 0, (int)R, nullptr, 0, 0, dot);
-  if (rc) return rc;
-  float* dmin = margin ? cur : nullptr;
-  rc = qpg_vq_argmin_f32(ctx, stream, z, dot, m->kk, R, m->emb, m->bins, ids, dmin, margin);
-  if (rc) return rc;
-  if (margin) {
-    qpg_launch_sub_inplace(stream, margin, dmin, R);
-    QPG_LAUNCH_CHECK("sub_inplace_kernel");
-  }
-  return QPG_OK;
-}
-
+// Encoder.forward (encdec.py:75-90) + BottleneckBlock.quantise
 extern "C" int qpg_vq_encode_f32(qpg_ctx* ctx, void* stream, const qpg_vq_model* m, const float* x, int B, int T,
                                  float* ws, int64_t ws_floats, int64_t* ids, float* latent, float* margin) {
   QPG_REQUIRE(ctx && model_ok(m) && x && ws && ids, "qpg_vq_encode_f32: bad argument");
@@ -634,34 +608,35 @@ extern "C" int qpg_vq_encode_f32(qpg_ctx* ctx, void* stream, const qpg_vq_model*
   QPG_REQUIRE(B >= 0 && T > 0 && T % hop == 0, "qpg_vq_encode_f32: T must be a multiple of %d", hop);
   QPG_REQUIRE(ws_floats >= qpg_vq_workspace_floats(m, B, T), "qpg_vq_encode_f32: workspace too small");
   if (B == 0) return QPG_OK;
-  int64_t cmax = m->width > m->emb ? m->width : m->emb;
-  if (m->bins > cmax) cmax = m->bins;
-  const int64_t slab = (((int64_t)B * T * cmax + 3) / 4) * 4;                          // T/2 rows suffice; keep simple
-  float *cur = ws, *alt = ws + slab, *h = ws + 2 * slab;
-  const SplitWs sw{ws + 3 * slab, ws_floats - 3 * slab};
-  if (tpath_ok(m, true)) return encode_tpath(ctx, stream, m, x, B, T, cur, alt, h, ids, latent, margin);
+  VqWalk w(ctx, stream, tpath_ok(m, true), m, B, T, ws, ws_floats);
   const float* in = x;
+  int rc;
+  if (w.tpath) {   // pose rows (135 floats = 540 B) -> 16-byte aligned rows of cin_pad floats
+    rc = qpg_pad_channels_f32(ctx, stream, x, (int64_t)B * T, m->in_dim, m->enc_down[0].cin_pad, w.h);
+    if (rc) return rc;
+    in = w.h;
+  }
   int Tc = T;
   for (int i = 0; i < m->down_t; ++i) {
     const int To = Tc / 2;
-    int rc = conv_call(ctx, stream, m->enc_down[i], in, B, Tc, 2, -1, 1, To, 1, 0, To, nullptr, 0, 0, alt, sw);
+    rc = w.conv(m->enc_down[i], in, B, Tc, 2, -1, 1, To, 1, 0, To, nullptr, 0, 0, w.alt);
     if (rc) return rc;
-    { float* t = cur; cur = alt; alt = t; }
+    w.swap();
     Tc = To;
-    rc = resnet_run(ctx, stream, m->enc_res[i], m->depth, m->growth, false, B, Tc, cur, alt, h, sw);
+    rc = w.resnet(m, m->enc_res[i], m->enc_res_pack[i], false, B, Tc);
     if (rc) return rc;
-    in = cur;
+    in = w.cur;
   }
-  float* z = latent ? latent : alt;
-  int rc = conv_call(ctx, stream, m->enc_out, cur, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, z, sw);
+  float* z = latent ? latent : w.alt;
+  rc = w.conv3(m->enc_out, w.cur, B, Tc, z);
   if (rc) return rc;
   // quantise: dot = z . k^T (1-tap conv over the flattened rows), then the argmin kernel
   const int64_t R = (int64_t)B * Tc;
   QPG_REQUIRE(R < 0x7fffffffll, "qpg_vq_encode_f32: too many latent rows");
-  float* dot = h;
-  rc = conv_call(ctx, stream, m->kT, z, 1, (int)R, 1, 0, 1, (int)R, 1, 0, (int)R, nullptr, 0, 0, dot, sw);
+  float* dot = w.h;
+  rc = w.conv(m->kT, z, 1, (int)R, 1, 0, 1, (int)R, 1, 0, (int)R, nullptr, 0, 0, dot);
   if (rc) return rc;
-  float* dmin = margin ? cur : nullptr;                                               // cur is free now
+  float* dmin = margin ? w.cur : nullptr;                                             // cur is free now
   rc = qpg_vq_argmin_f32(ctx, stream, z, dot, m->kk, R, m->emb, m->bins, ids, dmin, margin);
   if (rc) return rc;
   if (margin) {   // margin currently holds the runner-up distance: subtract the minimum in place
@@ -679,57 +654,36 @@ void qpg_launch_sub_inplace(void* stream, float* a, const float* b, int64_t n) {
   hipLaunchKernelGGL(sub_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, qpg_stream(stream), a, b, n);
 }
 
-static int decode_tpath(qpg_ctx* ctx, void* stream, const qpg_vq_model* m, const int64_t* ids, int B, int L, float* cur,
-                        float* alt, float* h, float* out, int32_t* status) {
-  int rc = qpg_vq_gather_f32(ctx, stream, m->k, ids, (int64_t)B * L, m->emb, m->bins, alt, status);   // dequantise
-  if (rc) return rc;
-  int Tc = L;
-  rc = convt_call(ctx, stream, m->dec_in, alt, 512, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, cur);
-  if (rc) return rc;
-  for (int i = 0; i < m->down_t; ++i) {
-    rc = resnet_tpath(ctx, stream, m->dec_res[i], m->dec_res_pack[i], m->depth, m->growth, m->reverse_dec != 0, B, Tc,
-                      cur, alt, h);
-    if (rc) return rc;
-    // ConvTranspose1d(k4,s2,p1): y[2m] = x[m-1].W3 + x[m].W1 ; y[2m+1] = x[m].W2 + x[m+1].W0
-    const qpg_conv_desc &ce = m->dec_up_even[i], &co = m->dec_up_odd[i];
-    rc = qpg_convt_pair_f32(ctx, stream, cur, B, Tc, 512, ce.wt, ce.b, -1, 0, co.wt, co.b, 0, 1, ce.taps, ce.cin_pad, ce.cout,
-                            ce.cout_pad, 1, 1, Tc, 2, 2 * Tc, alt);
-    if (rc) return rc;
-    { float* t = cur; cur = alt; alt = t; }
-    Tc *= 2;
-  }
-  return convt_call(ctx, stream, m->dec_out, cur, 512, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, out);
-}
-
+// Decoder.forward (encdec.py:115-136) on the dequantised codes
 extern "C" int qpg_vq_decode_f32(qpg_ctx* ctx, void* stream, const qpg_vq_model* m, const int64_t* ids, int B, int L,
                                  float* ws, int64_t ws_floats, float* out, int32_t* status) {
   QPG_REQUIRE(ctx && model_ok(m) && ids && ws && out, "qpg_vq_decode_f32: bad argument");
   QPG_REQUIRE(B >= 0 && L > 0 && (m->emb % 4) == 0, "qpg_vq_decode_f32: bad size");
-  const int hop = ipow(2, m->down_t);
-  const int T = L * hop;
+  const int T = L * ipow(2, m->down_t);
   QPG_REQUIRE(ws_floats >= qpg_vq_workspace_floats(m, B, T), "qpg_vq_decode_f32: workspace too small");
   if (B == 0) return QPG_OK;
-  int64_t cmax = m->width > m->emb ? m->width : m->emb;
-  if (m->bins > cmax) cmax = m->bins;
-  const int64_t slab = (((int64_t)B * T * cmax + 3) / 4) * 4;
-  float *cur = ws, *alt = ws + slab, *h = ws + 2 * slab;
-  const SplitWs sw{ws + 3 * slab, ws_floats - 3 * slab};
-  if (tpath_ok(m, false)) return decode_tpath(ctx, stream, m, ids, B, L, cur, alt, h, out, status);
-  int rc = qpg_vq_gather_f32(ctx, stream, m->k, ids, (int64_t)B * L, m->emb, m->bins, alt, status);   // dequantise
+  VqWalk w(ctx, stream, tpath_ok(m, false), m, B, T, ws, ws_floats);
+  int rc = qpg_vq_gather_f32(ctx, stream, m->k, ids, (int64_t)B * L, m->emb, m->bins, w.alt, status);   // dequantise
   if (rc) return rc;
   int Tc = L;
-  rc = conv_call(ctx, stream, m->dec_in, alt, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, cur, sw);
+  rc = w.conv3(m->dec_in, w.alt, B, Tc, w.cur);
   if (rc) return rc;
   for (int i = 0; i < m->down_t; ++i) {
-    rc = resnet_run(ctx, stream, m->dec_res[i], m->depth, m->growth, m->reverse_dec != 0, B, Tc, cur, alt, h, sw);
+    rc = w.resnet(m, m->dec_res[i], m->dec_res_pack[i], m->reverse_dec != 0, B, Tc);
     if (rc) return rc;
     // ConvTranspose1d(k4,s2,p1): y[2m] = x[m-1].W3 + x[m].W1 ; y[2m+1] = x[m].W2 + x[m+1].W0
-    rc = conv_call(ctx, stream, m->dec_up_even[i], cur, B, Tc, 1, -1, 1, Tc, 2, 0, 2 * Tc, nullptr, 0, 0, alt, sw);
+    const qpg_conv_desc &ce = m->dec_up_even[i], &co = m->dec_up_odd[i];
+    if (w.tpath) {   // both parities in one call
+      rc = qpg_convt_pair_f32(ctx, stream, w.cur, B, Tc, 512, ce.wt, ce.b, -1, 0, co.wt, co.b, 0, 1, ce.taps, ce.cin_pad,
+                              ce.cout, ce.cout_pad, 1, 1, Tc, 2, 2 * Tc, w.alt);
+    } else {
+      rc = w.conv(ce, w.cur, B, Tc, 1, -1, 1, Tc, 2, 0, 2 * Tc, nullptr, 0, 0, w.alt);
+      if (rc) return rc;
+      rc = w.conv(co, w.cur, B, Tc, 1, 0, 1, Tc, 2, 1, 2 * Tc, nullptr, 0, 0, w.alt);
+    }
     if (rc) return rc;
-    rc = conv_call(ctx, stream, m->dec_up_odd[i], cur, B, Tc, 1, 0, 1, Tc, 2, 1, 2 * Tc, nullptr, 0, 0, alt, sw);
-    if (rc) return rc;
-    { float* t = cur; cur = alt; alt = t; }
+    w.swap();
     Tc *= 2;
   }
-  return conv_call(ctx, stream, m->dec_out, cur, B, Tc, 1, -1, 1, Tc, 1, 0, Tc, nullptr, 0, 0, out, sw);
+  return w.conv3(m->dec_out, w.cur, B, Tc, out);
 }

@@ -10,6 +10,8 @@ Python only repacks the weights once (Conv1d (Cout,Cin,k) -> [k][Cin_pad][Cout_p
 (Cin,Cout,4) -> two 2-tap sets, one per output parity) and issues the layer sequence; every layer is a
 HIP kernel launch.  No torch.nn / cuDNN / MIOpen call, no CPU fallback.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -62,6 +64,35 @@ class _Conv:
         b = torch.zeros((self.cout_pad,), dtype=torch.float32)
         b[:cout] = bias
         self.w, self.b = w.to(dev).contiguous(), b.to(dev).contiguous()
+        self.wt = None                           # T-pack (VQVAE._tpack_all)
+        self._img16 = self._img16_buf = None     # split-f16 image (VQVAE._conv16_image)
+
+
+def layer_order(down_t, depth, growth, reverse):
+    """The network's layer sequence, stated once: (encoder, decoder) lists of (kind, state-dict name, slot, dilation).
+    Encoder (encdec.py:53-90): [down, res x depth] x down_t, conv3; decoder (encdec.py:93-136): conv3,
+    [res x depth, up] x down_t, conv3.  A resnet's block d dilates by growth ** d, in the decoder by growth ** (depth - 1 - d)
+    when `reverse` (resnet.py:57-62).  slot: where the layer sits in qpg_vq_model - the level of a down / up, (level, block)
+    of a res, the field's name of a conv3."""
+    e, d = "encoders.0.level_blocks.0.model", "decoders.0.level_blocks.0.model"
+    enc, dec = [], [("conv3", d + ".0", "dec_in", 1)]
+    for i in range(down_t):
+        enc.append(("down", "%s.%d.0" % (e, i), i, 1))
+        enc += [("res", "%s.%d.1.model.%d" % (e, i, j), (i, j), growth ** j) for j in range(depth)]
+        dec += [("res", "%s.%d.0.model.%d" % (d, i + 1, j), (i, j), growth ** (depth - 1 - j if reverse else j))
+                for j in range(depth)]
+        dec.append(("up", "%s.%d.1" % (d, i + 1), i, 1))
+    enc.append(("conv3", "%s.%d" % (e, down_t), "enc_out", 1))
+    dec.append(("conv3", "decoders.0.out", "dec_out", 1))
+    return enc, dec
+
+
+class _Layer:
+    """One record of a layer plan: layer_order's facts plus the packed convolutions - down (c,), res (c3, c1), conv3 (c,),
+    up (even, odd: the two output parities of the transposed convolution) - and a res block's fused T-pack image."""
+
+    def __init__(self, kind, name, slot, dil, convs):
+        self.kind, self.name, self.slot, self.dil, self.convs, self.pack = kind, name, slot, dil, convs, None
 
 
 class VQVAE:
@@ -88,13 +119,18 @@ class VQVAE:
         self.reg, self.vel, self.acc = float(_get(hps, "reg")), float(_get(hps, "vel")), float(_get(hps, "acc"))
         self.threshold = 1.0                                        # bottleneck.py:18
         self.training = False
+        self.train_fused = True          # training / eval forward() on the transposed-formulation kernels where T-packs exist
+        self.train_precision = "f32"     # "f16x3": the TRAINING forward's convolutions on the split-f16 kernels (opt-in)
         self.k_init, self.k_sum, self.k_elem = False, None, None    # BottleneckBlock.reset_k (bottleneck.py:20-24)
+        self._n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        self._saved = self._k_backup = None
         self._loaded = False
 
     # ------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict):
         """Accepts the reference checkpoint's `model_dict` (train.py:114-116; keys with or without the
-        DataParallel `module.` prefix) and repacks it for the kernels."""
+        DataParallel `module.` prefix) and repacks it for the kernels: the two layer plans (`enc_plan`, `dec_plan`) that
+        every walk over the network - parameters, descriptor, T-packs, forward, export - iterates."""
         sd = {}
         for k, v in state_dict.items():
             k = k[7:] if k.startswith("module.") else k
@@ -104,25 +140,28 @@ class VQVAE:
         def conv(name):               # nn.Conv1d weight (Cout, Cin, k) -> [k][Cin][Cout]
             return _Conv(sd[name + ".weight"].permute(2, 1, 0).contiguous(), sd[name + ".bias"], dev)
 
-        def resnet(name):
-            return [(conv("%s.model.%d.model.1" % (name, d)), conv("%s.model.%d.model.3" % (name, d)))
-                    for d in range(self.depth)]
-
-        enc = "encoders.0.level_blocks.0.model"
-        self.enc_down = [(conv("%s.%d.0" % (enc, i)), resnet("%s.%d.1" % (enc, i))) for i in range(self.down_t)]
-        self.enc_out = conv("%s.%d" % (enc, self.down_t))
-        dec = "decoders.0.level_blocks.0.model"
-        self.dec_in = conv(dec + ".0")
-        self.dec_up = []
-        for i in range(self.down_t):
-            wt = sd["%s.%d.1.weight" % (dec, i + 1)]            # ConvTranspose1d: (Cin, Cout, 4)
-            bt = sd["%s.%d.1.bias" % (dec, i + 1)]
+        def convs(kind, name):
+            if kind == "res":
+                return conv(name + ".model.1"), conv(name + ".model.3")
+            if kind != "up":
+                return (conv(name),)
+            wt, bt = sd[name + ".weight"], sd[name + ".bias"]       # ConvTranspose1d: (Cin, Cout, 4)
             # y[2m]   = x[m-1].W[:,:,3] + x[m].W[:,:,1]        (t = 2i - 1 + k, encdec.py:45: k4 s2 p1)
             # y[2m+1] = x[m].W[:,:,2]   + x[m+1].W[:,:,0]
-            even = _Conv(torch.stack((wt[:, :, 3], wt[:, :, 1])).contiguous(), bt, dev)
-            odd = _Conv(torch.stack((wt[:, :, 2], wt[:, :, 0])).contiguous(), bt, dev)
-            self.dec_up.append((resnet("%s.%d.0" % (dec, i + 1)), even, odd))
-        self.dec_out = conv("decoders.0.out")
+            return (_Conv(torch.stack((wt[:, :, 3], wt[:, :, 1])).contiguous(), bt, dev),
+                    _Conv(torch.stack((wt[:, :, 2], wt[:, :, 0])).contiguous(), bt, dev))
+
+        self.enc_plan, self.dec_plan = [[_Layer(kind, name, slot, dil, convs(kind, name)) for kind, name, slot, dil in order]
+                                        for order in layer_order(self.down_t, self.depth, self.growth, self.reverse)]
+        # the same convolutions by level, for whoever wants one layer (the kernel tests, tools/): enc_down[i] = (down,
+        # [(c3, c1), ...]), dec_up[i] = ([(c3, c1), ...], even, odd), and enc_out / dec_in / dec_out
+        def blocks(plan, i):
+            return [l.convs for l in plan if l.kind == "res" and l.slot[0] == i]
+        self.enc_down = [(l.convs[0], blocks(self.enc_plan, l.slot)) for l in self.enc_plan if l.kind == "down"]
+        self.dec_up = [(blocks(self.dec_plan, l.slot),) + l.convs for l in self.dec_plan if l.kind == "up"]
+        for l in self.enc_plan + self.dec_plan:
+            if l.kind == "conv3":
+                setattr(self, l.slot, l.convs[0])
         k = sd["bottleneck.level_blocks.0.k"]                   # (bins, emb)
         self.k = k.to(dev).contiguous()
         self.kT = _Conv(k.t().contiguous()[None], torch.zeros(self.bins), dev)      # x.k^T as a 1-tap "conv"
@@ -131,41 +170,41 @@ class VQVAE:
         self._flatten_parameters()
         self._tpack_all()
         self._desc = self._build_descriptor()
-        # split-K scratch of the per-layer path (the whole-network calls carve theirs out of the workspace)
+        # status words (they stay 0 between calls: cleared only after an error) and the fixed-size scratch: the split-K
+        # partial sums of the per-layer path (the whole-network calls carve theirs out of the workspace), the reductions'
+        self._dec_status = torch.zeros((1,), dtype=torch.int32, device=dev)      # a code id out of range
+        self._c16_status = torch.zeros((1,), dtype=torch.int32, device=dev)      # an activation beyond the f16 range
         self._split_ws = torch.empty((8 * 2048 * _pad(max(self.width, self.emb, self.bins), BN),), dtype=torch.float32,
                                      device=dev)
-        self.hl_latent_tol = None                # (measured per loaded set of weights; the conv objects - and their split-f16
-        self._img16_stale = False                #  images - are new)
+        self._rws = torch.empty((max(int(_lib.load().qpg_vq_reduce_ws_bytes()), 8 * self.bins),), dtype=torch.uint8,
+                                device=dev)
+        self._grown = {}                         # scratch that grows with the batch, or that only training needs (_buffer)
+        self._wgrad_floats = 32 * max(c.taps * c.cin_pad * c.cout_pad + c.cout_pad for c in self._convs)
+        self.hl_latent_tol = None                # (measured per loaded set of weights)
         self._loaded = True
         return self
 
+    def _buffer(self, name, n, dtype=torch.float32):
+        """Scratch `name` of at least n elements: kept between calls, replaced by a larger one when a call needs more."""
+        buf = self._grown.get(name)
+        if buf is None or buf.numel() < n:
+            buf = self._grown[name] = torch.empty((n,), dtype=dtype, device=self.device)
+        return buf
+
     def _flatten_parameters(self):
         """All trainable tensors (packed weights + biases) live in ONE flat buffer `self.param` with a matching
-        `self.grad`: one Adam launch and one gradient all-reduce per step.  The two parity sets of a transposed
-        convolution share their bias (ConvTranspose1d has one)."""
-        convs = []
-        for c, res in self.enc_down:
-            convs.append(c)
-            for c3, c1 in res:
-                convs += [c3, c1]
-        convs.append(self.enc_out)
-        n_enc_convs = len(convs)
-        convs.append(self.dec_in)
-        for res, even, odd in self.dec_up:
-            for c3, c1 in res:
-                convs += [c3, c1]
-            convs += [even, odd]
-        convs.append(self.dec_out)
-        shared = {id(odd): even for _, even, odd in self.dec_up}
-        total = 0
-        for c in convs:
-            total += c.w.numel() + (0 if id(c) in shared else c.b.numel())
+        `self.grad`: one Adam launch and one gradient all-reduce per step, in plan order - [0, n_enc_params) is the encoder.
+        The two parity sets of a transposed convolution share their bias (ConvTranspose1d has one)."""
+        enc = [c for l in self.enc_plan for c in l.convs]
+        self._convs = enc + [c for l in self.dec_plan for c in l.convs]
+        shared = {id(l.convs[1]): l.convs[0] for l in self.dec_plan if l.kind == "up"}
+        total = sum(c.w.numel() + (0 if id(c) in shared else c.b.numel()) for c in self._convs)
         self.param = torch.zeros((total,), dtype=torch.float32, device=self.device)
         self.grad = torch.zeros((total,), dtype=torch.float32, device=self.device)
         o = 0
-        for ci, c in enumerate(convs):
-            if ci == n_enc_convs:
-                self.n_enc_params = o                              # [0, n_enc_params) encoder, the rest decoder
+        for ci, c in enumerate(self._convs):
+            if ci == len(enc):
+                self.n_enc_params = o
             n = c.w.numel()
             self.param[o:o + n].copy_(c.w.view(-1))
             c.w, c.dw = self.param[o:o + n].view(c.w.shape), self.grad[o:o + n].view(c.w.shape)
@@ -177,12 +216,13 @@ class VQVAE:
                 self.param[o:o + n].copy_(c.b)
                 c.b, c.db = self.param[o:o + n], self.grad[o:o + n]
                 o += n
-        self._convs = convs
+
+    def _res_layers(self):
+        return [l for l in self.enc_plan + self.dec_plan if l.kind == "res"]
 
     def _tpack_all(self):
         """T-packed images of every convolution (inference kernels of csrc/qpg_convt.hip) and the fused
-        ResConv1DBlock images [k3 image NB=512 | 1x1 image NB=128].  They are copies: after a training step has
-        changed `self.param` call this again (encode()/decode() do so when `_tpack_stale` is set)."""
+        ResConv1DBlock images [k3 image NB=512 | 1x1 image NB=128].  They are copies of the weights: _weights_moved()."""
         self._tpack_stale = False
         self._tpack_on = self.width == 512 and self.emb == 512
         if not self._tpack_on:
@@ -190,12 +230,10 @@ class VQVAE:
         for c in self._convs + [self.kT]:
             ok = (c.taps * c.cin_pad) % 64 == 0
             c.wt = tpack(c.w[:, :c.cin, :c.cout], c.cin_pad, 128) if ok else None
-
-        def fused(res):
-            return [torch.cat((tpack(c3.w[:, :c3.cin, :c3.cout], c3.cin_pad, 512),
-                               tpack(c1.w[:, :c1.cin, :c1.cout], c1.cin_pad, 128))).contiguous() for c3, c1 in res]
-        self._enc_packs = [fused(res) for _, res in self.enc_down]
-        self._dec_packs = [fused(res) for res, _, _ in self.dec_up]
+        for l in self._res_layers():
+            c3, c1 = l.convs
+            l.pack = torch.cat((tpack(c3.w[:, :c3.cin, :c3.cout], c3.cin_pad, 512),
+                                tpack(c1.w[:, :c1.cin, :c1.cout], c1.cin_pad, 128))).contiguous()
 
     def _tpack_rebuild(self):
         """The same images again, IN PLACE and on the device (qpg_tpack_f32: one launch per convolution): the buffers -
@@ -206,30 +244,27 @@ class VQVAE:
             return
         dev = self.device
         for c in self._convs + [self.kT]:       # (kT.w is updated in place by the quantiser's refresh / EMA kernels)
-            if getattr(c, "wt", None) is not None:
+            if c.wt is not None:
                 _lib.call("qpg_tpack_f32", dev, c.w, c.taps, c.cin_pad, c.cout_pad, 128, c.wt)
-        for packs, ress in ((self._enc_packs, [res for _, res in self.enc_down]),
-                            (self._dec_packs, [res for res, _, _ in self.dec_up])):
-            for plist, res in zip(packs, ress):
-                for pack, (c3, c1) in zip(plist, res):
-                    n3 = c3.taps * c3.cin_pad * 512
-                    _lib.call("qpg_tpack_f32", dev, c3.w, c3.taps, c3.cin_pad, c3.cout_pad, 512, pack[:n3])
-                    _lib.call("qpg_tpack_f32", dev, c1.w, c1.taps, c1.cin_pad, c1.cout_pad, 128, pack[n3:])
+        for l in self._res_layers():
+            c3, c1 = l.convs
+            n3 = c3.taps * c3.cin_pad * 512
+            _lib.call("qpg_tpack_f32", dev, c3.w, c3.taps, c3.cin_pad, c3.cout_pad, 512, l.pack[:n3])
+            _lib.call("qpg_tpack_f32", dev, c1.w, c1.taps, c1.cin_pad, c1.cout_pad, 128, l.pack[n3:])
+
+    def _weights_moved(self):
+        """The one statement that a parameter or the codebook has changed (an optimiser step follows backward(); the EMA
+        update; init_k): whatever is a copy of the weights goes with it - the T-packs are stale, the split-f16 images are
+        dropped (re-packed at their next use), the measured latent tolerance is forgotten."""
+        self._tpack_stale = True
+        for c in self._convs + [self.kT]:
+            c._img16 = None
+        self.hl_latent_tol = None
 
     def _refresh_tpack(self):
-        """Every inference entry point calls this first (the f32 ones since round 3, the split-f16 ones since round 6 -
-        ADVICE r5: encode_latent('f16x3'), encode_f16x3(_device), _hl_tolerance and decode_f16x3 ran on the weight images
-        and the latent tolerance of the PREVIOUS weights after a training step): whatever is a copy of the weights - the
-        T-packs, the split-f16 images, the measured latent tolerance - is rebuilt or dropped when the weights have moved."""
-        if getattr(self, "_tpack_stale", False):
+        """Every entry point that reads the T-packs calls this first: rebuilt when the weights have moved."""
+        if self._tpack_stale:
             self._tpack_rebuild()
-            self._drop_conv16_images()           # (the split-f16 images are copies of the weights too)
-            self.hl_latent_tol = None
-            self._img16_stale = False
-        elif getattr(self, "_img16_stale", False) and getattr(self, "_loaded", False):
-            self._drop_conv16_images()
-            self.hl_latent_tol = None
-            self._img16_stale = False
 
     def parameters(self):
         """(param, grad) flat buffers — what optim.Adam(model.parameters()) iterates in the reference (train.py:71)."""
@@ -246,27 +281,20 @@ class VQVAE:
         def fill(d, c):
             d.w, d.b = c.w.data_ptr(), c.b.data_ptr()
             d.taps, d.cin, d.cin_pad, d.cout, d.cout_pad = c.taps, c.cin, c.cin_pad, c.cout, c.cout_pad
-            wt = getattr(c, "wt", None) if self._tpack_on else None
-            d.wt = wt.data_ptr() if wt is not None else None
-        if self._tpack_on:
-            for i in range(self.down_t):
-                for d in range(self.depth):
-                    m.enc_res_pack[i][d] = self._enc_packs[i][d].data_ptr()
-                    m.dec_res_pack[i][d] = self._dec_packs[i][d].data_ptr()
-        for i, (c, res) in enumerate(self.enc_down):
-            fill(m.enc_down[i], c)
-            for d, (c3, c1) in enumerate(res):
-                fill(m.enc_res[i][d][0], c3)
-                fill(m.enc_res[i][d][1], c1)
-        fill(m.enc_out, self.enc_out)
-        fill(m.dec_in, self.dec_in)
-        for i, (res, even, odd) in enumerate(self.dec_up):
-            for d, (c3, c1) in enumerate(res):
-                fill(m.dec_res[i][d][0], c3)
-                fill(m.dec_res[i][d][1], c1)
-            fill(m.dec_up_even[i], even)
-            fill(m.dec_up_odd[i], odd)
-        fill(m.dec_out, self.dec_out)
+            d.wt = c.wt.data_ptr() if self._tpack_on and c.wt is not None else None
+        for side, plan in (("enc", self.enc_plan), ("dec", self.dec_plan)):
+            for l in plan:
+                if l.kind == "res":
+                    i, j = l.slot
+                    fill(getattr(m, side + "_res")[i][j][0], l.convs[0])
+                    fill(getattr(m, side + "_res")[i][j][1], l.convs[1])
+                    if self._tpack_on:
+                        getattr(m, side + "_res_pack")[i][j] = l.pack.data_ptr()
+                elif l.kind == "up":
+                    fill(m.dec_up_even[l.slot], l.convs[0])
+                    fill(m.dec_up_odd[l.slot], l.convs[1])
+                else:
+                    fill(m.enc_down[l.slot] if l.kind == "down" else getattr(m, l.slot), l.convs[0])
         fill(m.kT, self.kT)
         m.k, m.kk = self.k.data_ptr(), self.kk.data_ptr()
         return m
@@ -276,10 +304,7 @@ class VQVAE:
         n = _lib.load().qpg_vq_workspace_floats(ctypes.byref(self._desc), B, T)
         if n < 0:
             raise RuntimeError("qpg_vq_workspace_floats failed")
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws.numel() < n:
-            self._ws = ws = torch.empty((n,), dtype=torch.float32, device=self.device)
-        return ws
+        return self._buffer("ws", n)
 
     def encode_fused(self, x, return_latent=False, return_margin=False):
         """One C call for the whole encoder + quantiser (qpg_vq_encode_f32)."""
@@ -301,89 +326,106 @@ class VQVAE:
         return out if len(out) > 1 else ids
 
     # ------------------------------------------------------------------------------------------
-    def _conv(self, c, x, B, T_in, T_out, in_stride=1, in_offset=0, dil=1, out=None, out_stride=1, out_offset=0,
-              T_y=None, residual=None, relu_in=False, relu_out=False):
-        T_y = T_out if T_y is None else T_y
-        if out is None:
-            out = torch.empty((B, T_y, c.cout), dtype=torch.float32, device=self.device)
-        _lib.call("qpg_conv1d_f32", self.device, x, B, T_in, c.cin, c.w, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad,
-                  in_stride, in_offset, dil, T_out, out_stride, out_offset, T_y, residual, int(relu_in), int(relu_out),
-                  out, self._split_ws, self._split_ws.numel())
-        return out
-
-    def _resnet(self, blocks, x, B, T, reverse):
-        for d, (c3, c1) in enumerate(blocks):
-            dil = self.growth ** (self.depth - 1 - d if reverse else d)              # resnet.py:57-62
-            h = self._conv(c3, x, B, T, T, in_offset=-dil, dil=dil, relu_in=True, relu_out=True)
-            x = self._conv(c1, h, B, T, T, residual=x)                                # x + conv1(relu(conv3(relu(x))))
-        return x
-
-    # ------------------------------------------------------------------------------------------
-    # split-operand f16 convolutions (round 5, csrc/qpg_conv16.hip): the same layers at ~3/16 of the f32 matrix time per
-    # flop, agreeing with the f32 kernels to ~1e-5 - NOT bit-identical, so they serve under a margin check (encode below)
+    # one convolution, on one of three kernel families:
+    #   "f32"    qpg_conv1d_f32, the LDS-tiled f32 matrix-core kernel (exact f32 FMA chains)
+    #   "t"      qpg_convt_f32, the transposed formulation reading the T-pack (another summation order: agrees to f32 rounding)
+    #   "f16x3"  qpg_conv16_f32, split-operand f16 (round 5, csrc/qpg_conv16.hip): ~3/16 of the f32 matrix time per flop,
+    #            within ~1e-5 of the f32 kernels - NOT bit-identical, so it serves under a margin / range check
     # ------------------------------------------------------------------------------------------
     WEXP_FROM_IMAGE = _lib.QPG_CONV16_WEXP_FROM_IMAGE          # the kernel reads the scale exponent from the image
 
+    def _padded(self, x, rows, width):
+        """x (.., C) with its rows zero-padded to `width` channels (a copy; x itself when C == width)."""
+        if x.shape[-1] == width:
+            return x
+        xp = torch.empty(x.shape[:-1] + (width,), dtype=torch.float32, device=self.device)
+        _lib.call("qpg_pad_channels_f32", self.device, x, rows, x.shape[-1], width, xp)
+        return xp
+
     def _conv16_image(self, c, read_exp=True):
         """(image, scale exponent) of convolution c for qpg_conv16_f32; built on first use, dropped when the weights change.
-        read_exp=False (the training forward: the weights change every step): no host read-back - the exponent slot holds
-        WEXP_FROM_IMAGE and the kernel takes it from the image."""
-        img = getattr(c, "_img16", None)
-        if img is None:
-            lib = _lib.load()
-            nb = int(lib.qpg_conv16_image_bytes(c.taps, _pad(c.cin, 8), c.cout))
-            buf = getattr(c, "_img16_buf", None)              # (re-packed in place step after step)
-            if buf is None or buf.numel() != nb:
-                buf = c._img16_buf = torch.empty((nb,), dtype=torch.uint8, device=self.device)
+        read_exp=False (the weights change every step, or nothing may synchronise): no host read-back - the exponent slot
+        holds WEXP_FROM_IMAGE and the kernel takes it from the image."""
+        if c._img16 is None:
+            nb = int(_lib.load().qpg_conv16_image_bytes(c.taps, _pad(c.cin, 8), c.cout))
+            if c._img16_buf is None:                          # (re-packed in place step after step)
+                c._img16_buf = torch.empty((nb,), dtype=torch.uint8, device=self.device)
             # (channels are padded to a multiple of 8 on the activation side: the 135-channel pose rows become 136 wide)
             _lib.call("qpg_conv16_pack_weights", self.device, c.w, c.taps, _pad(c.cin, 8), c.cin_pad, c.cout, c.cout_pad,
-                      buf, nb)
-            img = c._img16 = (buf, None)
-        if read_exp and img[1] is None:
-            buf = img[0]
+                      c._img16_buf, nb)
+            c._img16 = (c._img16_buf, None)
+        buf, w_exp = c._img16
+        if not read_exp:
+            return buf, self.WEXP_FROM_IMAGE
+        if w_exp is None:
             nb = buf.numel()
-            img = c._img16 = (buf, int(buf[nb - 64:nb - 60].view(torch.int32).item()))
-        return img
+            w_exp = int(buf[nb - 64:nb - 60].view(torch.int32).item())
+            c._img16 = (buf, w_exp)
+        return buf, w_exp
 
-    def _drop_conv16_images(self):
-        for c in self._convs + [self.kT]:
-            c._img16 = None
-
-    def _conv16(self, c, x, B, T_in, T_out, in_stride=1, in_offset=0, dil=1, residual=None, relu_in=False, relu_out=False):
-        img, w_exp = self._conv16_image(c)
-        out = torch.empty((B, T_out, c.cout), dtype=torch.float32, device=self.device)
-        st = getattr(self, "_c16_status", None)
-        if st is None:
-            st = self._c16_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        _lib.call("qpg_conv16_f32", self.device, x, B, T_in, x.shape[-1], _pad(c.cin, 8), img, w_exp, c.b, c.taps, c.cout,
-                  in_stride, in_offset, dil, T_out, 1, 0, T_out, residual, int(relu_in), int(relu_out), out, st)
-        return out
-
-    def _conv16_fwd(self, c, x, B, T_in, T_out, in_stride=1, in_offset=0, dil=1, out=None, out_stride=1, out_offset=0,
-                    T_y=None, residual=None, relu_in=False, relu_out=False):
-        """A training-forward convolution on the split-f16 kernel (train_precision "f16x3"): _conv_fwd's arguments, the
-        exponent read on the device, the out-of-range status accumulated in self._c16_status (checked by backward())."""
-        img, _ = self._conv16_image(c, read_exp=False)
-        if x.shape[-1] % 8:                           # pose rows (135 floats) -> 136
-            xp = torch.empty((B, T_in, _pad(x.shape[-1], 8)), dtype=torch.float32, device=self.device)
-            _lib.call("qpg_pad_channels_f32", self.device, x, B * T_in, x.shape[-1], xp.shape[-1], xp)
-            x = xp
+    def _conv(self, c, x, B, T_in, T_out, in_stride=1, in_offset=0, dil=1, out=None, out_stride=1, out_offset=0,
+              T_y=None, residual=None, relu_in=False, relu_out=False, kernel="f32", read_exp=True):
+        """out[b, t * out_stride + out_offset] = conv c of x at t * in_stride + in_offset (taps `dil` apart), relu before /
+        after, + residual.  x keeps its own channel count (a tape's weight gradient reads it): "t" gets a copy padded to
+        Cin_pad, "f16x3" to a multiple of 8 (pose rows: 135 -> 136), when they differ.  "f16x3": out-of-range activations
+        accumulate in self._c16_status; read_exp, see _conv16_image.  "t" without a T-pack for c runs "f32"."""
         T_y = T_out if T_y is None else T_y
         if out is None:
             out = torch.empty((B, T_y, c.cout), dtype=torch.float32, device=self.device)
-        st = getattr(self, "_c16_status", None)
-        if st is None:
-            st = self._c16_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        _lib.call("qpg_conv16_f32", self.device, x, B, T_in, x.shape[-1], _pad(c.cin, 8), img, self.WEXP_FROM_IMAGE, c.b,
-                  c.taps, c.cout, in_stride, in_offset, dil, T_out, out_stride, out_offset, T_y, residual, int(relu_in),
-                  int(relu_out), out, st)
+        geom = (in_stride, in_offset, dil, T_out, out_stride, out_offset, T_y, residual, int(relu_in), int(relu_out), out)
+        if kernel == "f16x3":
+            img, w_exp = self._conv16_image(c, read_exp)
+            if x.shape[-1] % 8:
+                x = self._padded(x, B * T_in, _pad(x.shape[-1], 8))
+            _lib.call("qpg_conv16_f32", self.device, x, B, T_in, x.shape[-1], _pad(c.cin, 8), img, w_exp, c.b, c.taps, c.cout,
+                      *geom, self._c16_status)
+        elif kernel == "t" and c.wt is not None:
+            x = self._padded(x, B * T_in, c.cin_pad)
+            _lib.call("qpg_convt_f32", self.device, x, B, T_in, c.cin_pad, c.wt, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad,
+                      *geom)
+        elif kernel in ("f32", "t"):
+            _lib.call("qpg_conv1d_f32", self.device, x, B, T_in, c.cin, c.w, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad,
+                      *geom, self._split_ws, self._split_ws.numel())
+        else:
+            raise ValueError("kernel must be 'f32', 't' or 'f16x3'")
         return out
 
-    def _resnet16(self, blocks, x, B, T, reverse):
-        for d, (c3, c1) in enumerate(blocks):
-            dil = self.growth ** (self.depth - 1 - d if reverse else d)              # resnet.py:57-62
-            h = self._conv16(c3, x, B, T, T, in_offset=-dil, dil=dil, relu_in=True, relu_out=True)
-            x = self._conv16(c1, h, B, T, T, residual=x)
+    def _fused_block_fills_chip(self, B, T):
+        """The rule of VqWalk::resnet (csrc/qpg_vqvae.hip): the fused block kernel where its 64-position tiles fill the chip."""
+        return ((B * T + 63) // 64) * 4 >= self._n_cu * 3
+
+    def _walk(self, plan, x, B, T, kernel, tape=None, read_exp=True):
+        """Run a layer plan (enc_plan: Encoder.forward, encdec.py:75-90, (B,T,C) -> (B,T/8,emb); dec_plan: Decoder.forward,
+        encdec.py:115-136, (B,L,emb) -> (B,8L,C)) layer by layer on one kernel family, channels-last.  tape: a list that
+        receives (layer, input, hidden activation of a res block, T_in) per layer - what _bwd_tape needs."""
+        conv = functools.partial(self._conv, kernel=kernel, read_exp=read_exp)
+        for l in plan:
+            h, T_out = None, T
+            if l.kind == "down":                                    # k4 s2 p1
+                T_out = T // self.stride_t
+                y = conv(l.convs[0], x, B, T, T_out, in_stride=self.stride_t, in_offset=-(self.stride_t // 2))
+            elif l.kind == "conv3":                                 # k3 s1 p1
+                y = conv(l.convs[0], x, B, T, T, in_offset=-1)
+            elif l.kind == "res":                                   # x + conv1(relu(conv3_dil(relu(x))))
+                c3, c1 = l.convs
+                if kernel == "t" and self._fused_block_fills_chip(B, T):
+                    # one launch: the hidden activation is written for the backward pass
+                    y, h = torch.empty_like(x), torch.empty_like(x)
+                    _lib.call("qpg_resblock_f32", self.device, x, B, T, l.dil, l.pack, c3.b, c1.b, y, h)
+                else:
+                    # (on "t": a short level - T = 30 at B = 256: 480 waves of 16 positions for 1024 SIMDs - takes the
+                    # two-launch form, as qpg_vq_encode_f32 does below the same threshold: 0.17 against 0.27 ms per block)
+                    h = conv(c3, x, B, T, T, in_offset=-l.dil, dil=l.dil, relu_in=True, relu_out=True)
+                    y = conv(c1, h, B, T, T, residual=x)
+            else:                                                   # "up": the two parities of ConvTranspose1d k4 s2 p1
+                even, odd = l.convs
+                T_out = 2 * T
+                y = torch.empty((B, T_out, even.cout), dtype=torch.float32, device=self.device)
+                conv(even, x, B, T, T, in_offset=-1, out=y, out_stride=2, out_offset=0, T_y=T_out)
+                conv(odd, x, B, T, T, in_offset=0, out=y, out_stride=2, out_offset=1, T_y=T_out)
+            if tape is not None:
+                tape.append((l, x, h, T))
+            x, T = y, T_out
         return x
 
     def encode_latent(self, x, precision="f32"):
@@ -394,22 +436,11 @@ class VQVAE:
         self._refresh_tpack()
         x = x.to(self.device, torch.float32).contiguous()
         B, T, C = x.shape
-        if precision == "f16x3":
-            if C % 8:                                # pose rows (135 floats) -> 136: 16-byte aligned 8-channel fragments
-                xp = torch.empty((B, T, _pad(C, 8)), dtype=torch.float32, device=self.device)
-                _lib.call("qpg_pad_channels_f32", self.device, x, B * T, C, _pad(C, 8), xp)
-                x = xp
-            conv, resnet = self._conv16, self._resnet16
-        elif precision == "f32":
-            conv, resnet = self._conv, self._resnet
-        else:
+        if precision not in ("f32", "f16x3"):
             raise ValueError("precision must be 'f32' or 'f16x3'")
-        for c, res in self.enc_down:
-            T_out = T // self.stride_t
-            x = conv(c, x, B, T, T_out, in_stride=self.stride_t, in_offset=-(self.stride_t // 2))
-            T = T_out
-            x = resnet(res, x, B, T, False)
-        return conv(self.enc_out, x, B, T, T, in_offset=-1)
+        if precision == "f16x3":                     # pose rows (135 floats) -> 136: 16-byte aligned 8-channel fragments
+            x = self._padded(x, B * T, _pad(C, 8))   # (ahead of the first layer's weight image, as always)
+        return self._walk(self.enc_plan, x, B, T, precision)
 
     def encode_f16x3(self, x, return_stats=False):
         """VQVAE.encode on the split-f16 kernels with the f32 path as the referee (VERDICT r4 #5's bound-and-recheck):
@@ -423,9 +454,9 @@ class VQVAE:
         x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         tol = self._hl_tolerance(x.shape[1])
-        self._c16_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._c16_status.zero_()
         z = self.encode_latent(x, precision="f16x3")
-        ids, dmin, dsec = self._quantise_with_distances(z)
+        ids, dmin, dsec = self._quantise(z, True, True)
         # d' - d <= 2 tol sqrt(d) + tol^2 for either distance (|z' - z| <= tol): the order of the two best is safe when
         # their gap exceeds the sum of what each can move by
         slack = 2.0 * tol * (dmin.clamp_min(0).sqrt() + dsec.clamp_min(0).sqrt()) + 2.0 * tol * tol
@@ -448,15 +479,13 @@ class VQVAE:
         capture)."""
         assert self._loaded, "load_state_dict first"
         self._refresh_tpack()                    # (weights moved since the tolerance was measured: it is gone, see below)
-        assert getattr(self, "hl_latent_tol", None) is not None, "call _hl_tolerance(T) first (again after a training step)"
+        assert self.hl_latent_tol is not None, "call _hl_tolerance(T) first (again after a training step)"
         tol = float(self.hl_latent_tol)
         B = x.shape[0]
-        st = getattr(self, "_c16_status", None)
-        if st is None:
-            st = self._c16_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        st = self._c16_status
         st.zero_()
         z = self.encode_latent(x, precision="f16x3")
-        ids, dmin, dsec = self._quantise_with_distances(z)
+        ids, dmin, dsec = self._quantise(z, True, True)
         slack = 2.0 * tol * (dmin.clamp_min(0).sqrt() + dsec.clamp_min(0).sqrt()) + 2.0 * tol * tol
         unsure = ((dsec - dmin) <= slack).view(B, -1).any(dim=1)
         flags = (unsure | (st != 0)).to(torch.int32)
@@ -472,22 +501,24 @@ class VQVAE:
             ids[redo] = self.encode_fused(x[sel].contiguous()).cpu().numpy()
         return ids, int(redo.size)
 
-    def _quantise_with_distances(self, z):
+    def _quantise(self, z, want_dmin=False, want_dsec=False):
+        """BottleneckBlock.quantise's distances (bottleneck.py:120-126) on a channels-last latent (B,L,emb): the x.k^T GEMM and
+        the argmin kernel -> (ids int64, distance to the nearest code or None, to the runner-up or None), each (B,L)."""
         B, L, E = z.shape
         R = B * L
         z2 = z.contiguous().view(1, R, E)
         dot = self._conv(self.kT, z2, 1, R, R)
-        ids = torch.empty((R,), dtype=torch.int64, device=self.device)
-        dmin = torch.empty((R,), dtype=torch.float32, device=self.device)
-        dsec = torch.empty((R,), dtype=torch.float32, device=self.device)
+        ids = torch.empty((B, L), dtype=torch.int64, device=self.device)
+        dmin = torch.empty((B, L), dtype=torch.float32, device=self.device) if want_dmin else None
+        dsec = torch.empty((B, L), dtype=torch.float32, device=self.device) if want_dsec else None
         _lib.call("qpg_vq_argmin_f32", self.device, z2, dot, self.kk, R, E, self.bins, ids, dmin, dsec)
-        return ids.view(B, L), dmin.view(B, L), dsec.view(B, L)
+        return ids, dmin, dsec
 
     def _hl_tolerance(self, T):
         """Bound on |z_f16x3 - z_f32| (row-wise l2) assumed by encode_f16x3: 8 x the largest difference measured on a probe
         batch of standard-normal pose windows, once per loaded set of weights."""
         self._refresh_tpack()
-        tol = getattr(self, "hl_latent_tol", None)
+        tol = self.hl_latent_tol
         if tol is None:
             g = torch.Generator(device="cpu").manual_seed(20260929)
             probe = torch.randn((8, T, self.input_dim), generator=g).to(self.device)
@@ -499,17 +530,8 @@ class VQVAE:
 
     def quantise(self, z, return_margin=False):
         """BottleneckBlock.quantise on a channels-last latent (B,L,emb) -> ids (B,L) int64."""
-        B, L, E = z.shape
-        R = B * L
-        z2 = z.contiguous().view(1, R, E)
-        dot = self._conv(self.kT, z2, 1, R, R)
-        ids = torch.empty((R,), dtype=torch.int64, device=self.device)
-        dmin = torch.empty((R,), dtype=torch.float32, device=self.device) if return_margin else None
-        dsec = torch.empty((R,), dtype=torch.float32, device=self.device) if return_margin else None
-        _lib.call("qpg_vq_argmin_f32", self.device, z2, dot, self.kk, R, E, self.bins, ids, dmin, dsec)
-        if return_margin:
-            return ids.view(B, L), (dsec - dmin).view(B, L)
-        return ids.view(B, L)
+        ids, dmin, dsec = self._quantise(z, return_margin, return_margin)
+        return (ids, dsec - dmin) if return_margin else ids
 
     def encode(self, x, start_level=0, end_level=None, bs_chunks=1):
         """VQVAE.encode (vqvae.py:174-181): returns [LongTensor (B, T/8)]."""
@@ -527,9 +549,7 @@ class VQVAE:
         for ids in torch.chunk(torch.as_tensor(zs[0]), bs_chunks, dim=0):
             ids = ids.to(self.device, torch.int64).contiguous()
             B, L = ids.shape
-            status = getattr(self, "_dec_status", None)          # stays 0 between calls: cleared only after an error
-            if status is None:
-                status = self._dec_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            status = self._dec_status
             T = L * self.hop
             ws = self._workspace(B, T)
             out = torch.empty((B, T, self.input_dim), dtype=torch.float32, device=self.device)
@@ -563,21 +583,10 @@ class VQVAE:
             # sequences take the f32 kernels - this entry point is never slower than decode() now; force=True: measurements)
             out = self.decode(zs)
             return (out, {"activation_outside_f16_range": False, "routed_to_f32_kernels": True}) if return_stats else out
-        st = getattr(self, "_c16_status", None)
-        if st is None:
-            st = self._c16_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        gst = getattr(self, "_dec_status", None)
-        if gst is None:
-            gst = self._dec_status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        st, gst = self._c16_status, self._dec_status
         zq = torch.empty((B * L, self.emb), dtype=torch.float32, device=self.device)
         _lib.call("qpg_vq_gather_f32", self.device, self.k, ids, B * L, self.emb, self.bins, zq, gst)
-        was_training, self.training = self.training, False
-        self._force16 = True
-        try:
-            out = self.decode_latent(zq.view(B, L, self.emb), B, L)
-        finally:
-            self._force16 = False
-            self.training = was_training
+        out = self.decode_latent(zq.view(B, L, self.emb), B, L, kernel="f16x3")
         flags = torch.stack((gst[0], st[0])).cpu().numpy()              # ONE read-back for both words
         if int(flags[0]):
             gst.zero_()
@@ -592,11 +601,7 @@ class VQVAE:
     # VQVAE.forward (vqvae.py:183-302): training / validation step
     # ------------------------------------------------------------------------------------------
     def _red_ws(self):
-        ws = getattr(self, "_rws", None)
-        if ws is None:
-            n = max(int(_lib.load().qpg_vq_reduce_ws_bytes()), 8 * self.bins)
-            self._rws = ws = torch.empty((n,), dtype=torch.uint8, device=self.device)
-        return ws
+        return self._rws
 
     def _gather_rows(self, table, idx):
         idx = idx.to(self.device, torch.int64).contiguous()
@@ -612,23 +617,24 @@ class VQVAE:
 
     def _refresh_quantiser(self):
         """kT / kk follow k (after init_k)."""
-        self._tpack_stale = True
+        self._weights_moved()
         self.kT.w[0, :self.emb, :self.bins].copy_(self.k.t())
         self._code_norms()
 
-    def _init_k(self, z2):
-        """BottleneckBlock.init_k (bottleneck.py:39-49): k <- random rows of the first batch (tiled with noise when the
-        batch has fewer rows than codes, bottleneck.py:26-37).  The permutation comes from torch's CPU generator, as
-        in the reference, and is broadcast from rank 0 (bottleneck.py:44)."""
+    def _random_rows(self, z2):
+        """`bins` random rows of the batch, tiled with noise first when it has fewer rows than codes (bottleneck.py:26-37).
+        The noise, then the permutation, come from torch's generators as in the reference (bottleneck.py:44: the rows are
+        broadcast from rank 0 by the caller)."""
         R, E = z2.shape
         y = z2
         if R < self.bins:
-            n_rep = (self.bins + R - 1) // R
-            y = z2.repeat(n_rep, 1)
+            y = z2.repeat((self.bins + R - 1) // R, 1)
             y = y + torch.randn_like(y) * (0.01 / np.sqrt(E))
-        perm = torch.randperm(y.shape[0])[:self.bins]
-        k = parallel.broadcast_(self._gather_rows(y.contiguous(), perm), 0)
-        self.k.copy_(k)
+        return self._gather_rows(y.contiguous(), torch.randperm(y.shape[0])[:self.bins])
+
+    def _init_k(self, z2):
+        """BottleneckBlock.init_k (bottleneck.py:39-49): k <- random rows of the first batch."""
+        self.k.copy_(parallel.broadcast_(self._random_rows(z2), 0))
         self.k_sum = self.k.clone()
         self.k_elem = torch.ones((self.bins,), dtype=torch.float32, device=self.device)
         self.k_init = True
@@ -640,112 +646,23 @@ class VQVAE:
         R, E = z2.shape
         bsum = torch.empty((self.bins, E), dtype=torch.float32, device=self.device)
         belem = torch.empty((self.bins,), dtype=torch.float32, device=self.device)
-        need = int(_lib.load().qpg_vq_code_sums_ws_bytes(R, E, self.bins))
-        cws = getattr(self, "_cws", None)
-        if cws is None or cws.numel() < need:
-            self._cws = cws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        cws = self._buffer("code_sums", int(_lib.load().qpg_vq_code_sums_ws_bytes(R, E, self.bins)), torch.uint8)
         _lib.call("qpg_vq_code_sums_f32", self.device, z2, ids, R, E, self.bins, bsum, belem, cws, cws.numel())
-        y = z2
-        if R < self.bins:
-            n_rep = (self.bins + R - 1) // R
-            y = z2.repeat(n_rep, 1)
-            y = y + torch.randn_like(y) * (0.01 / np.sqrt(E))
-        k_rand = self._gather_rows(y.contiguous(), torch.randperm(y.shape[0])[:self.bins])
+        k_rand = self._random_rows(z2)
         parallel.broadcast_(k_rand, 0)
         parallel.allreduce_sum_(bsum)
         parallel.allreduce_sum_(belem)
         out = torch.empty((4,), dtype=torch.float32, device=self.device)
         ws = self._red_ws()
-        self._tpack_stale = True
+        self._weights_moved()
         _lib.call("qpg_vq_ema_update_f32", self.device, self.k, self.k_sum, self.k_elem, bsum, belem, k_rand, self.mu,
                   self.threshold, self.bins, E, self.kT.w, self.kT.cout_pad, self.kk, ws, ws.numel(), out)
         return out
 
-    def _fused_block_fills_chip(self, B, T):
-        """resnet_tpath's rule (csrc/qpg_vqvae.hip): the fused block kernel where its 64-position tiles fill the chip."""
-        n_cu = self.__dict__.get("_n_cu")
-        if n_cu is None:
-            n_cu = self.__dict__["_n_cu"] = torch.cuda.get_device_properties(self.device).multi_processor_count
-        return ((B * T + 63) // 64) * 4 >= n_cu * 3
-
-    def _train16(self):
-        """The training step's FORWARD convolutions on the split-f16 kernels (train_precision = "f16x3"; round 5, opt-in:
-        three f16 MFMAs per f32 product, f32 accumulation - within ~1e-5 of the f32 kernels, not bit-identical; the backward
-        pass stays on the f32 kernels, reading the activations this forward recorded)."""
-        return (self.training and getattr(self, "train_precision", "f32") == "f16x3") or getattr(self, "_force16", False)
-
-    def _res_fwd(self, blocks, x, B, T, reverse, tape, packs=None):
-        for d, (c3, c1) in enumerate(blocks):
-            dil = self.growth ** (self.depth - 1 - d if reverse else d)              # resnet.py:57-62
-            if packs is not None and self._fused_block_fills_chip(B, T) and not self._train16():
-                # one launch: the hidden activation is written for the backward pass
-                y, h = torch.empty_like(x), torch.empty_like(x)
-                _lib.call("qpg_resblock_f32", self.device, x, B, T, dil, packs[d], c3.b, c1.b, y, h)
-            elif packs is not None:
-                # short level (T = 30 at B = 256: 480 waves of 16 positions for 1024 SIMDs): the two-launch form on the
-                # transposed kernels, as qpg_vq_encode_f32 does below the same threshold (0.17 against 0.27 ms per block)
-                h = self._conv_fwd(c3, x, B, T, T, True, in_offset=-dil, dil=dil, relu_in=True, relu_out=True)
-                y = self._conv_fwd(c1, h, B, T, T, True, residual=x)
-            elif self._train16():
-                h = self._conv16_fwd(c3, x, B, T, T, in_offset=-dil, dil=dil, relu_in=True, relu_out=True)
-                y = self._conv16_fwd(c1, h, B, T, T, residual=x)
-            else:
-                h = self._conv(c3, x, B, T, T, in_offset=-dil, dil=dil, relu_in=True, relu_out=True)
-                y = self._conv(c1, h, B, T, T, residual=x)
-            tape.append(("res", c3, c1, x, h, dil, T))
-            x = y
-        return x
-
-    def _conv_fwd(self, c, x, B, T_in, T_out, fused, **kw):
-        """A training-forward convolution: on the transposed-formulation kernel (qpg_convt_f32, from the T-pack that
-        _tpack_rebuild refreshed) when `fused`, else qpg_conv1d_f32.  x keeps its own channel count on the tape (the
-        weight gradient reads it); the transposed kernel gets a copy padded to Cin_pad when the two differ."""
-        if self._train16():
-            return self._conv16_fwd(c, x, B, T_in, T_out, **kw)
-        wt = getattr(c, "wt", None) if fused else None
-        if wt is None:
-            return self._conv(c, x, B, T_in, T_out, **kw)
-        xin = x
-        if x.shape[-1] != c.cin_pad:
-            xin = torch.empty((B, T_in, c.cin_pad), dtype=torch.float32, device=self.device)
-            _lib.call("qpg_pad_channels_f32", self.device, x, B * T_in, x.shape[-1], c.cin_pad, xin)
-        T_y = kw.get("T_y") or T_out
-        out = kw.get("out")
-        if out is None:
-            out = torch.empty((B, T_y, c.cout), dtype=torch.float32, device=self.device)
-        _lib.call("qpg_convt_f32", self.device, xin, B, T_in, c.cin_pad, wt, c.b, c.taps, c.cin_pad, c.cout, c.cout_pad,
-                  kw.get("in_stride", 1), kw.get("in_offset", 0), kw.get("dil", 1), T_out, kw.get("out_stride", 1),
-                  kw.get("out_offset", 0), T_y, kw.get("residual"), int(kw.get("relu_in", False)),
-                  int(kw.get("relu_out", False)), out)
-        return out
-
-    def _encoder_fwd(self, x, B, T, tape, fused=False):
-        """Encoder.forward (encdec.py:75-90), recording what the backward pass needs."""
-        for i, (c, res) in enumerate(self.enc_down):
-            T_out = T // self.stride_t
-            y = self._conv_fwd(c, x, B, T, T_out, fused, in_stride=self.stride_t, in_offset=-(self.stride_t // 2))
-            tape.append(("down", c, x, T))
-            x, T = self._res_fwd(res, y, B, T_out, False, tape, self._enc_packs[i] if fused else None), T_out
-        z = self._conv_fwd(self.enc_out, x, B, T, T, fused, in_offset=-1)
-        tape.append(("conv3", self.enc_out, x, T))
-        return z
-
-    def decode_latent(self, zq, B, L, tape=None, fused=False):
-        """Decoder.forward (encdec.py:115-136) on a channels-last quantised latent (B,L,emb) -> (B, 8L, C)."""
-        tape = [] if tape is None else tape
-        T = L
-        x = self._conv_fwd(self.dec_in, zq, B, T, T, fused, in_offset=-1)
-        tape.append(("conv3", self.dec_in, zq, T))
-        for i, (res, even, odd) in enumerate(self.dec_up):
-            x = self._res_fwd(res, x, B, T, self.reverse, tape, self._dec_packs[i] if fused else None)
-            y = torch.empty((B, 2 * T, even.cout), dtype=torch.float32, device=self.device)
-            self._conv_fwd(even, x, B, T, T, fused, in_offset=-1, out=y, out_stride=2, out_offset=0, T_y=2 * T)
-            self._conv_fwd(odd, x, B, T, T, fused, in_offset=0, out=y, out_stride=2, out_offset=1, T_y=2 * T)
-            tape.append(("up", even, odd, x, T))
-            x, T = y, 2 * T
-        out = self._conv_fwd(self.dec_out, x, B, T, T, fused, in_offset=-1)
-        tape.append(("conv3", self.dec_out, x, T))
-        return out
+    def decode_latent(self, zq, B, L, tape=None, kernel="f32"):
+        """Decoder.forward (encdec.py:115-136) on a channels-last quantised latent (B,L,emb) -> (B, 8L, C), layer by layer on
+        one kernel family ("f16x3": the weight images' exponents stay on the device)."""
+        return self._walk(self.dec_plan, zq, B, L, kernel, tape, read_exp=False)
 
     def forward(self, x):
         """VQVAE.forward (vqvae.py:183-302): x (B,T,C) -> (x_out (B,T,C), loss, metrics).  In training mode the
@@ -756,38 +673,34 @@ class VQVAE:
         x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
         B, T, C = x.shape
         enc_tape, dec_tape = [], []
-        # training forward on the transposed-formulation kernels (round 3): their T-packs are refreshed on the device
-        # from the weights the optimiser has just updated; activations are recorded as before
-        fused = bool(getattr(self, "train_fused", True) and self._tpack_on)
-        if self._train16():
-            # split-f16 forward: the weight images are re-packed (in place, no host read-back) from the weights the
-            # optimiser has just updated; the T-packs stay stale until an f32 / inference call needs them
-            if getattr(self, "_tpack_stale", False) or getattr(self, "_img16_stale", True):
-                self._drop_conv16_images()
-                self._img16_stale = False
-        elif fused:
+        # The kernel family of this call's convolutions, chosen here and nowhere else.  "f16x3" (train_precision, training
+        # only, opt-in since round 5): three f16 MFMAs per f32 product, f32 accumulation - within ~1e-5 of the f32 kernels,
+        # not bit-identical; the weight images are re-packed (in place, no host read-back) from the weights the optimiser
+        # has just updated, the T-packs stay stale until an f32 / inference call needs them, and the backward pass stays
+        # on the f32 kernels, reading the activations this forward recorded.  "t" (train_fused, round 3): the
+        # transposed-formulation kernels, their T-packs refreshed on the device first.
+        f16x3 = self.training and self.train_precision == "f16x3"
+        kernel = "f16x3" if f16x3 else "t" if self.train_fused and self._tpack_on else "f32"
+        if kernel == "t":
             self._refresh_tpack()
-        z = self._encoder_fwd(x, B, T, enc_tape, fused)             # (B,L,E) channels-last
+        z = self._walk(self.enc_plan, x, B, T, kernel, enc_tape, read_exp=False)      # (B,L,E) channels-last
         L, E = z.shape[1], z.shape[2]
         R = B * L
         z2 = z.view(R, E)
         if self.training and not self.k_init:
             self._init_k(z2)
         # quantise with the current codebook (bottleneck.py:166), dequantise BEFORE the EMA update (:169)
-        dot = self._conv(self.kT, z2.view(1, R, E), 1, R, R)
-        ids = torch.empty((R,), dtype=torch.int64, device=self.device)
-        dmin = torch.empty((R,), dtype=torch.float32, device=self.device)
-        _lib.call("qpg_vq_argmin_f32", self.device, z2, dot, self.kk, R, E, self.bins, ids, dmin, None)
+        ids, dmin, _ = self._quantise(z, want_dmin=True)
         zq = self._gather_rows(self.k, ids)
         stats = torch.empty((3,), dtype=torch.float32, device=self.device)      # commit, fit, prenorm
         ws = self._red_ws()
         _lib.call("qpg_vq_latent_stats_f32", self.device, z2, zq, dmin, R, E, ws, ws.numel(), stats)
-        if self._train16():
+        if f16x3:
             # (the EMA below moves the codebook inside forward(): kept aside so that a step whose split-f16 forward turns
             # out to have left the f16 range - backward() reports it - can be redone in f32 from the same state)
             self._k_backup = [t.clone() for t in (self.k, self.k_sum, self.k_elem, self.kT.w, self.kk)]
-        ema = self._update_k(z2, ids) if self.training else None
-        x_out = self.decode_latent(zq.view(B, L, E), B, L, dec_tape, fused)
+        ema = self._update_k(z2, ids.view(R)) if self.training else None
+        x_out = self.decode_latent(zq.view(B, L, E), B, L, dec_tape, kernel)
         out6 = torch.empty((6,), dtype=torch.float32, device=self.device)
         _lib.call("qpg_vq_loss_f32", self.device, x_out, x, B, T, C, stats[0:1], self.commit, self.reg, self.vel,
                   self.acc, ws, ws.numel(), out6)
@@ -796,19 +709,15 @@ class VQVAE:
         if self.training:
             q = dict(fit=stats[1], pn=stats[2], entropy=ema[0], used_curr=ema[1], usage=ema[2], dk=ema[3])
             metrics.update({kk: torch.floor(v) for kk, v in q.items()})        # sum(..) // len(..) with one level
-        self._saved = dict(x=x, z2=z2, zq=zq, ids=ids.view(B, L), x_out=x_out, enc=enc_tape, dec=dec_tape,
-                           B=B, T=T, L=L, f16x3=self._train16()) if self.training else None
+        self._saved = dict(x=x, z2=z2, zq=zq, ids=ids, x_out=x_out, enc=enc_tape, dec=dec_tape,
+                           B=B, T=T, L=L, f16x3=f16x3) if self.training else None
         return x_out, out6[0], metrics
 
     # ------------------------------------------------------------------------------------------
     # backward of forward(): what `loss.backward()` (train.py:128) computes, into the flat gradient buffer
     # ------------------------------------------------------------------------------------------
     def _wgrad_ws(self):
-        ws = getattr(self, "_gws", None)
-        if ws is None:
-            big = max(c.taps * c.cin_pad * c.cout_pad + c.cout_pad for c in self._convs)
-            self._gws = ws = torch.empty((32 * big,), dtype=torch.float32, device=self.device)
-        return ws
+        return self._buffer("wgrad", self._wgrad_floats)   # (100 MB at full width: only a training run allocates it)
 
     def _wgrad(self, c, x, dy, B, T_in, T_out, in_stride=1, in_offset=0, dil=1, out_stride=1, out_offset=0, T_y=None,
                relu_in=False, acc_bias=False):
@@ -828,23 +737,23 @@ class VQVAE:
         return out
 
     def _bwd_tape(self, tape, dy, B, need_input_grad=True):
-        """Walk a forward tape backwards; dy = gradient w.r.t. the tape's last output."""
+        """Walk a forward tape (_walk) backwards; dy = gradient w.r.t. the tape's last output."""
         for i in range(len(tape) - 1, -1, -1):
-            op = tape[i]
+            l, x, h, T = tape[i]
             last = i == 0 and not need_input_grad
-            if op[0] == "conv3":                                    # k3 s1 p1 convolution
-                _, c, x, T = op
+            if l.kind == "conv3":                                   # k3 s1 p1 convolution
+                c, = l.convs
                 self._wgrad(c, x, dy, B, T, T, in_offset=-1)
                 if not last:
                     dy = self._dgrad(c, dy, B, T, T, 3, 2, -1, in_offset=-1)
-            elif op[0] == "res":                                    # y = x + conv1(relu(conv3_dil(relu(x))))
-                _, c3, c1, x, h, dil, T = op
+            elif l.kind == "res":                                   # y = x + conv1(relu(conv3_dil(relu(x))))
+                (c3, c1), dil = l.convs, l.dil
                 self._wgrad(c1, h, dy, B, T, T)
                 dh = self._dgrad(c1, dy, B, T, T, 1, 0, 1, gate=h)
                 self._wgrad(c3, x, dh, B, T, T, in_offset=-dil, dil=dil, relu_in=True)
                 dy = self._dgrad(c3, dh, B, T, T, 3, 2, -1, in_offset=-dil, dil=dil, gate=x, residual=dy)
-            elif op[0] == "down":                                   # k4 s2 p1 convolution, T -> T/2
-                _, c, x, T = op
+            elif l.kind == "down":                                  # k4 s2 p1 convolution, T -> T/2
+                c, = l.convs
                 To = T // 2
                 self._wgrad(c, x, dy, B, T, To, in_stride=2, in_offset=-1)
                 if not last:
@@ -852,14 +761,12 @@ class VQVAE:
                     self._dgrad(c, dy, B, To, To, 2, 3, -2, in_offset=-1, out_stride=2, out_offset=0, T_y=T, out=dx)
                     self._dgrad(c, dy, B, To, To, 2, 2, -2, in_offset=0, out_stride=2, out_offset=1, T_y=T, out=dx)
                     dy = dx
-            elif op[0] == "up":                                     # ConvTranspose1d k4 s2 p1 as two parity sets
-                _, even, odd, x, T = op
+            else:                                                   # "up": ConvTranspose1d k4 s2 p1 as two parity sets
+                even, odd = l.convs
                 self._wgrad(even, x, dy, B, T, T, in_offset=-1, out_stride=2, out_offset=0, T_y=2 * T)
                 self._wgrad(odd, x, dy, B, T, T, in_offset=0, out_stride=2, out_offset=1, T_y=2 * T, acc_bias=True)
                 dx = self._dgrad(even, dy, B, 2 * T, T, 2, 1, -1, in_stride=2, in_offset=0, dil=2)
                 dy = self._dgrad(odd, dy, B, 2 * T, T, 2, 1, -1, in_stride=2, in_offset=-1, dil=2, residual=dx, out=dx)
-            else:
-                raise AssertionError(op[0])
         return dy
 
     def loss_grad(self, x_out, x, upstream=1.0):
@@ -876,8 +783,7 @@ class VQVAE:
         d_x_out: optional replacement for the loss terms' own d loss / d x_out.
         sync_grads: data-parallel averaging of the gradients in two buckets — the decoder half is all-reduced while
         the encoder half is still being computed (backward produces the decoder's gradients first)."""
-        self._tpack_stale = True          # an optimiser step follows: the T-packed inference images go stale
-        self._img16_stale = True
+        self._weights_moved()             # (an optimiser step follows)
         sv = self._saved
         assert sv is not None, "backward() needs a training-mode forward() first"
         B, T, L = sv["B"], sv["T"], sv["L"]
@@ -933,25 +839,18 @@ class VQVAE:
             out[prefix + name + ".weight"] = W(c)[:, :c.cin, :c.cout].permute(2, 1, 0).contiguous().cpu()
             out[prefix + name + ".bias"] = Bv(c)[:c.cout].clone().cpu()
 
-        def put_res(name, blocks):
-            for d, (c3, c1) in enumerate(blocks):
-                put("%s.model.%d.model.1" % (name, d), c3)
-                put("%s.model.%d.model.3" % (name, d), c1)
-
-        enc = "encoders.0.level_blocks.0.model"
-        for i, (c, res) in enumerate(self.enc_down):
-            put("%s.%d.0" % (enc, i), c)
-            put_res("%s.%d.1" % (enc, i), res)
-        put("%s.%d" % (enc, self.down_t), self.enc_out)
-        dec = "decoders.0.level_blocks.0.model"
-        put(dec + ".0", self.dec_in)
-        for i, (res, even, odd) in enumerate(self.dec_up):
-            put_res("%s.%d.0" % (dec, i + 1), res)
-            e = W(even)[:, :even.cin, :even.cout]
-            o = W(odd)[:, :odd.cin, :odd.cout]
-            out["%s%s.%d.1.weight" % (prefix, dec, i + 1)] = torch.stack((o[1], e[1], o[0], e[0]), dim=2).contiguous().cpu()
-            out["%s%s.%d.1.bias" % (prefix, dec, i + 1)] = Bv(even)[:even.cout].clone().cpu()
-        put("decoders.0.out", self.dec_out)
+        for l in self.enc_plan + self.dec_plan:
+            if l.kind == "res":
+                put(l.name + ".model.1", l.convs[0])
+                put(l.name + ".model.3", l.convs[1])
+            elif l.kind == "up":
+                even, odd = l.convs
+                e = W(even)[:, :even.cin, :even.cout]
+                o = W(odd)[:, :odd.cin, :odd.cout]
+                out[prefix + l.name + ".weight"] = torch.stack((o[1], e[1], o[0], e[0]), dim=2).contiguous().cpu()
+                out[prefix + l.name + ".bias"] = Bv(even)[:even.cout].clone().cpu()
+            else:
+                put(l.name, l.convs[0])
         if not grads:
             out[prefix + "bottleneck.level_blocks.0.k"] = self.k.clone().cpu()
         return out

@@ -120,9 +120,9 @@ def merge_mixed_by_hand(recv, W, src_stride, dist_off, idx_off, Q, K, eps1, eps2
     return d, ix, rk, stats.cpu().numpy(), counts
 
 
-def decode_layers(m, ids):
-    """Layer-by-layer decode through the per-layer entry points (qpg_vq_gather_f32 + qpg_conv1d_f32): same result as
-    VQVAE.decode(), which makes ONE C call."""
+def decode_layers(m, ids, kernel="f32"):
+    """Layer-by-layer decode through the per-layer entry points (qpg_vq_gather_f32, then the model's walk over its decoder
+    plan on one kernel family; "f32": qpg_conv1d_f32): same result as VQVAE.decode(), which makes ONE C call."""
     import torch
     from qpgesture_amd import _lib
     ids = torch.as_tensor(ids).to(m.device, torch.int64).contiguous()
@@ -130,12 +130,4 @@ def decode_layers(m, ids):
     status = torch.zeros((1,), dtype=torch.int32, device=m.device)
     x = torch.empty((B, L, m.emb), dtype=torch.float32, device=m.device)
     _lib.call("qpg_vq_gather_f32", m.device, m.k, ids, B * L, m.emb, m.bins, x, status)
-    T = L
-    x = m._conv(m.dec_in, x, B, T, T, in_offset=-1)
-    for res, even, odd in m.dec_up:
-        x = m._resnet(res, x, B, T, m.reverse)
-        y = torch.empty((B, 2 * T, even.cout), dtype=torch.float32, device=m.device)
-        m._conv(even, x, B, T, T, in_offset=-1, out=y, out_stride=2, out_offset=0, T_y=2 * T)
-        m._conv(odd, x, B, T, T, in_offset=0, out=y, out_stride=2, out_offset=1, T_y=2 * T)
-        x, T = y, 2 * T
-    return m._conv(m.dec_out, x, B, T, T, in_offset=-1)
+    return m._walk(m.dec_plan, x, B, L, kernel)

@@ -187,6 +187,42 @@ def test_reference_config_loads():
     assert cfg.VQVAE.width == 512 and cfg.VQVAE.downs_t == [3] and len(cfg.data_mean) == 135
 
 
+def test_vqvae_layer_order():
+    """vqvae.layer_order, the one statement of the network's layer sequence (a pure function, no device): kinds in the
+    order of encdec.py, dilations growth ** d per resnet (resnet.py:57-62), reversed in the decoder on request, and the
+    state-dict names in the order of the reference's state_dict()."""
+    from qpgesture_amd import synth
+    from qpgesture_amd.vqvae import layer_order
+
+    def kinds(plan):
+        return [l[0] for l in plan]
+
+    def dils(plan):
+        d = [l[3] for l in plan if l[0] == "res"]
+        return [d[i:i + depth] for i in range(0, len(d), depth)]
+
+    depth = 3
+    enc, dec = layer_order(3, 3, 3, True)
+    assert kinds(enc) == ["down", "res", "res", "res"] * 3 + ["conv3"]
+    assert kinds(dec) == ["conv3"] + ["res", "res", "res", "up"] * 3 + ["conv3"]
+    assert dils(enc) == [[1, 3, 9]] * 3 and dils(dec) == [[9, 3, 1]] * 3
+    assert all(l[3] == 1 for l in enc + dec if l[0] != "res")
+    assert [l[2] for l in enc if l[0] == "res"] == [(i, j) for i in range(3) for j in range(3)]
+    assert [l[2] for l in dec if l[0] != "res"] == ["dec_in", 0, 1, 2, "dec_out"]
+    assert dils(layer_order(3, 3, 3, False)[1]) == [[1, 3, 9]] * 3
+    names = []                              # what the records' names expand to: the reference's parameter order
+    for kind, name, _, _ in enc + dec:
+        names += [name + ".model.1", name + ".model.3"] if kind == "res" else [name]
+    ref = [k[7:-7] for k in synth.make_vqvae_state_dict(7) if k.endswith(".weight")]
+    assert names == ref and len(names) == 45
+    depth = 4
+    enc, dec = layer_order(2, 4, 2, True)
+    assert kinds(enc) == ["down"] + ["res"] * 4 + ["down"] + ["res"] * 4 + ["conv3"]
+    assert kinds(dec) == ["conv3"] + (["res"] * 4 + ["up"]) * 2 + ["conv3"]
+    assert dils(enc) == [[1, 2, 4, 8]] * 2 and dils(dec) == [[8, 4, 2, 1]] * 2
+    assert dils(layer_order(2, 4, 2, False)[1]) == [[1, 2, 4, 8]] * 2
+
+
 def test_training_host_logic_without_gpu():
     """Host-side pieces of the training loop that need no device: the reference-shaped initial state_dict
     (names/shapes of a fresh reference model, torch default init bounds), MultiStepLR, the CLI parser and config."""

@@ -35,7 +35,7 @@ print("B=%d encode: fused f32 %.3f ms (%.0f TF/s) | layerwise f32 %.3f | layerwi
 c3 = m.enc_down[0][1][0][0]
 h = torch.randn((B, 120, 512), device=dev)
 t32 = timed(lambda: m._conv(c3, h, B, 120, 120, in_offset=-1, dil=1, relu_in=True, relu_out=True))
-t16 = timed(lambda: m._conv16(c3, h, B, 120, 120, in_offset=-1, dil=1, relu_in=True, relu_out=True))
+t16 = timed(lambda: m._conv(c3, h, B, 120, 120, in_offset=-1, dil=1, relu_in=True, relu_out=True, kernel="f16x3"))
 fl = 2.0 * B * 120 * 1536 * 512 / 1e9
 print("k3 512->512 T=120 B=%d: LDS-tiled f32 %.3f ms (%.0f TF/s) | conv16 %.3f ms (%.0f TF/s f32-equivalent, %.0f TF/s f16 issued)"
       % (B, t32, fl / t32, t16, fl / t16, 3 * fl / t16))

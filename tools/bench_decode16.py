@@ -32,11 +32,7 @@ for B, L in ((1, 180), (1, 30)):
         def body():
             from qpgesture_amd import _lib
             _lib.call("qpg_vq_gather_f32", dev, m.k, ids, B * L, m.emb, m.bins, zq, m._dec_status)
-            m._force16 = True
-            try:
-                return m.decode_latent(zq.view(B, L, m.emb), B, L)
-            finally:
-                m._force16 = False
+            return m.decode_latent(zq.view(B, L, m.emb), B, L, kernel="f16x3")
         body(); torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):

@@ -1,5 +1,6 @@
 """What one matching step launches, as data: every C-ABI launch (_lib.call and the launch half of _lib.prepare), every
-torch.cuda.Event.record and every Stream.wait_event / wait_stream, in host order, for a grid of matcher configurations.
+torch.cuda.Event.record and every Stream.wait_event / wait_stream, in host order, for a grid of matcher configurations and
+for the VQ-VAE's entry points (`vqvae/*`: inference, training steps, the refresh after one).
 
     python tools/launch_trace.py out.json            # {cell: [entry, ...]}; prints the number of entries per cell
     python tools/launch_trace.py --diff a.json b.json   # exit status 1 and the first differing entry of every unequal cell
@@ -129,8 +130,62 @@ def tensors(A):
             torch.from_numpy(np.ascontiguousarray(A["te_ctx"], np.float32)).to(dev))
 
 
+def vqvae_cells(cells):
+    """The codec's entry points, on a full-width model (T-packed kernels) and a reduced-width one (no T-packs: the f32
+    per-layer kernels; the split-f16 entry points are exercised at full width only, like everywhere else in the project).
+    Two shapes: (8, 3200) frames - resnet levels of 1600 / 800 / 400 positions, on both sides of the fused-block rule with
+    256 CUs - and (1, 360), below it on every level."""
+    from qpgesture_amd.optim import Adam
+    from qpgesture_amd.vqvae import VQVAE
+
+    def cell(name, fn):
+        cells[name] = traced(fn)
+        print("%-44s %4d entries" % (name, len(cells[name])), flush=True)
+
+    def step(m, opt, x):
+        m(x)
+        m.backward()
+        opt.step()
+
+    small = dict(width=64, emb_width=64, l_bins=96)
+    for mname, hps in (("w512", None), ("w64", small)):
+        for B, T in ((8, 3200), (1, 360)):
+            torch.manual_seed(11)                                       # (init_k / update_k draw from the CPU generator)
+            m = VQVAE(hps, 135, device=dev).load_state_dict(synth.make_vqvae_state_dict(7, hps))
+            x = torch.randn((B, T, 135), device=dev, generator=torch.Generator(device=dev).manual_seed(6))
+            ids = m.encode(x)[0]
+            pre = "vqvae/%s/%dx%d/" % (mname, B, T)
+            cell(pre + "encode", lambda: m.encode(x))
+            cell(pre + "encode_latent/f32", lambda: m.encode_latent(x))
+            cell(pre + "quantise/margin", lambda: m.quantise(m.encode_latent(x), return_margin=True))
+            cell(pre + "decode", lambda: m.decode([ids[:, :30]]))
+            cell(pre + "forward/eval", lambda: m.eval()(x))
+            if hps is None:
+                cell(pre + "encode_latent/f16x3", lambda: m.encode_latent(x, precision="f16x3"))
+                cell(pre + "encode_f16x3", lambda: m.encode_f16x3(x))
+                cell(pre + "encode_f16x3_device", lambda: m.encode_f16x3_device(x))
+                cell(pre + "decode_f16x3/force", lambda: m.decode_f16x3([ids], force=True))
+            opt = Adam(m.parameters(), lr=1e-4, betas=(0.5, 0.999))
+            m.train()
+            for fused in (True, False):
+                m.train_fused = fused
+                cell(pre + "train/2_steps/fused=%d" % fused, lambda: (step(m, opt, x), step(m, opt, x)))
+            m.train_fused = True
+            if hps is None:
+                m.train_precision = "f16x3"
+                cell(pre + "train/step/f16x3", lambda: step(m, opt, x))
+                m.train_precision = "f32"
+                m.eval()
+                cell(pre + "after_step/decode_f16x3", lambda: m.decode_f16x3([ids], force=True))
+                m.train()
+                step(m, opt, x)
+            m.eval()
+            cell(pre + "after_step/encode", lambda: m.encode(x))
+
+
 def main(out_path):
     cells = {}
+    vqvae_cells(cells)
     A = fixture_arrays(96, 3, 5, 6, 7, 8)
     M = 3
     te_i, te_c = tensors(A)
