@@ -422,7 +422,9 @@ static int text_percode(qpg_ctx* ctx, void* stream, const float* xt, const float
     hipLaunchKernelGGL(text_fill_ff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, qpg_stream(stream), partial, n);
     QPG_LAUNCH_CHECK("text_fill_ff_kernel");
   }
-  if (tiles_per_chunk == 1) {      // LDS-free organisation: one tile per block, NG query groups share it
+  // No candidate (ntile == 0): neither organisation sweeps - a zero-block grid is not a valid launch - and the merge turns
+  // the filled table into `absent` / -1 everywhere.
+  if (ntile > 0 && tiles_per_chunk == 1) {      // LDS-free organisation: one tile per block, NG query groups share it
     constexpr int QG = 12, NW = 8;
     const int64_t nqb = (Q + QG * NW - 1) / (QG * NW);
     const dim3 grid((unsigned)(((ntile + 7) / 8) * nqb * 8));
@@ -433,7 +435,7 @@ static int text_percode(qpg_ctx* ctx, void* stream, const float* xt, const float
       hipLaunchKernelGGL((text_cosine_gmin_f32_kernel<QG, NW, false>), grid, dim3(64 * NW), 0, qpg_stream(stream), xt, C, Dm,
                          cand_code, K, qn, Q, idx_base, partial, nrm);
     QPG_LAUNCH_CHECK("text_cosine_gmin_f32_kernel");
-  } else if (nchunk > 0) {
+  } else if (ntile > 0) {
     hipLaunchKernelGGL((text_cosine_percode_f32_kernel<QB, NG>), dim3((unsigned)nchunk, (unsigned)((Q + QB - 1) / QB)),
                        dim3(64 * NG), sh, qpg_stream(stream), xt, C, Dm, cand_code, K, qn, Q, tiles_per_chunk, idx_base,
                        partial);
