@@ -956,6 +956,57 @@ int qpg_conv1d_bwd_weight_f32(qpg_ctx*, void* stream, const float* x, int B, int
                               int T_out, int out_stride, int out_offset, int T_y, int relu_in, float* dw, float* db,
                               int accumulate_bias, float* ws, int64_t ws_floats);
 
+/* ---- WavLM feature extraction (process/WavLM/WavLM.py extract_features, inference, no masks): the stage kernels that
+ * qpgesture_amd/wavlm.py chains.  All arrays [dev] f32, activations channels-last rows [B][T][C]; every matrix product is
+ * a k-ordered f32 FMA chain on the f32 matrix cores, so no result depends on the batch it is computed in.  Supported:
+ * extractor_mode "layer_norm", layer_norm_first, gelu, gated relative-position bias, head dim QPG_WAVLM_HEAD_DIM, at
+ * most QPG_WAVLM_MAX_FRAMES frames per window in the transformer. ---- */
+#define QPG_WAVLM_HEAD_DIM 64
+#define QPG_WAVLM_MAX_FRAMES 256
+
+/* Output frames of an unpadded Conv1d: (t_in - k) / s + 1, 0 if t_in < k. */
+int64_t qpg_wavlm_conv_frames(int64_t t_in, int k, int s);
+
+/* Layer 0 of the conv feature extractor (WavLM.py:400-403, Conv1d(1, C, k, stride s)): wav [B][n] raw samples,
+ * w [C][k], bias [C] or NULL; out [B][T0][C], T0 = qpg_wavlm_conv_frames(n, k, s), before the layer's norm. */
+int qpg_wavlm_conv0_f32(qpg_ctx*, void* stream, const float* wav, int B, int64_t n, const float* w, const float* bias,
+                        int C, int k, int s, float* out);
+
+/* LayerNorm over each of M rows of C (biased variance of the centred values, eps inside the root), times gamma plus
+ * beta, then the exact (erf) GELU if gelu != 0.  y may be x. */
+int qpg_wavlm_layernorm_f32(qpg_ctx*, void* stream, const float* x, const float* gamma, const float* beta, int64_t M,
+                            int C, float eps, int gelu, float* y);
+
+/* The one GEMM of the model, batched over z = (outer o, inner i), o < n_outer, i < n_inner:
+ *   out_z[m][n] = f(sum_k A_z[m][k] W_i[n][k] + bias_i[n]) + residual_z[m][n],   m < M, n < N, f = GELU if gelu != 0
+ * A_z = A + o a_outer + i a_inner with row stride lda (rows may overlap: a strided convolution over channels-last input
+ * is this with lda = stride * C and K = taps * C), W_i = W + i w_inner rows of K, bias_i = bias + i bias_inner (NULL: no
+ * bias), out_z = out + o c_outer + i c_inner with row stride ldc; residual (NULL: none) is laid out like out and may be
+ * out.  The sum over k is taken in chains of 512 products whose results are added in k order.  K must be a multiple of
+ * 16 (QPG_EUNSUP otherwise); A, W 16-byte aligned, their strides multiples of 4 floats. */
+int qpg_wavlm_gemm_f32(qpg_ctx*, void* stream, const float* A, int64_t lda, const float* W, const float* bias,
+                       const float* residual, float* out, int64_t ldc, int M, int N, int K, int gelu, int n_outer,
+                       int n_inner, int64_t a_outer, int64_t a_inner, int64_t w_inner, int64_t bias_inner, int64_t c_outer,
+                       int64_t c_inner);
+
+/* Input image of pos_conv (WavLM.py:514-527: grouped Conv1d, padding taps / 2, an even kernel's last frame dropped):
+ * padded [B][groups][T + taps - 1][D / groups], row r of group g = x[b][r - taps / 2][g D / groups ..], zero outside the
+ * clip.  Output frame t of a group is then the GEMM row that starts at its row t (lda = D / groups, K = taps D / groups). */
+int qpg_wavlm_pos_pad_f32(qpg_ctx*, void* stream, const float* x, int B, int T, int D, int groups, int taps,
+                          float* padded);
+
+/* Gated relative-position factor (modules.py:523-533): x_ln [M][H][64] the layer-normed block input, grep_w [8][64],
+ * grep_b [8], grep_a [H]; gate [M][H] = a (b grep_a[h] - 1) + 2 with a, b = sigmoid of the sums of outputs 0..3, 4..7. */
+int qpg_wavlm_gate_f32(qpg_ctx*, void* stream, const float* x_ln, const float* grep_w, const float* grep_b,
+                       const float* grep_a, int64_t M, int H, float* gate);
+
+/* Self-attention of one block: qkv [B T][3 H 64] (q | k | v, q already scaled by 64^-0.5), gate [B T][H], relb
+ * [2T - 1][H] the position-bias table (entry k - q + T - 1: bias of key k seen from query q), out [B T][H 64] =
+ * softmax_k(q k^T + gate[q] relb[k - q]) v per (batch, head), the row maximum subtracted before exp.  The (T, T) scores
+ * live in LDS only.  T > QPG_WAVLM_MAX_FRAMES: QPG_EUNSUP, nothing launched. */
+int qpg_wavlm_attention_f32(qpg_ctx*, void* stream, const float* qkv, const float* gate, const float* relb, int B, int T,
+                            int H, float* out);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

@@ -1,13 +1,17 @@
-"""Drop-in for step 3 of the reference's process/make_beat_dataset.py (:261-325, :604-607): encode every
-240-frame pose window of a speaker database to 30 gesture codes.
+"""Drop-in for step 3 of the reference's process/make_beat_dataset.py (:261-385, :604-607): encode every
+240-frame pose window of a speaker database to 30 gesture codes (dataset_to_code) and, with --WavLM_model_path, every
+4 s audio window to its WavLM features (wav_to_wavlm) - the two halves of the reference's step 3.
 
     python -m qpgesture_amd.make_beat_dataset --config codebook.yml --save_dir ../dataset/BEAT \
-        --prefix speaker_10_state_0 --gpu 0 --step 3 --VQVAE_model_path codebook_checkpoint_best.bin
+        --prefix speaker_10_state_0 --gpu 0 --step 3 --VQVAE_model_path codebook_checkpoint_best.bin \
+        --WavLM_model_path WavLM-Large.pt
 
 Reads  <save_dir>/<prefix>/<prefix>_<split>_240.npz['body'] (N,240,135) for split in train/validation/test,
 writes <save_dir>/<prefix>/<prefix>_<split>_240_code.npz['code'] int64 (N,30) — the files GestureKNN.py takes
-as --train_codebook.  Same flags as codebook/configs/parse_args.py.  Steps 1, 2 and 4 (BVH/audio/text
-preprocessing with third-party models) are out of scope.
+as --train_codebook.  With --WavLM_model_path ({'cfg', 'model'} checkpoint) it also reads the same files' ['wav']
+(N,64000) and writes <prefix>_<split>_240_WavLM.npz['wavlm'] f32 (N,199,D), the --train_wavlm files, through the HIP
+WavLM of qpgesture_amd/wavlm.py; without the flag nothing else changes.  Same flags as codebook/configs/parse_args.py.
+Steps 1, 2 and 4 (BVH cutting, vq-wav2vec and sentence embeddings) are out of scope.
 
 The reference encodes one window per call in a Python loop (:314-316); windows are independent, so they are
 encoded in batches of 256 on the GPU (qpg_vq_encode_f32)."""
@@ -31,6 +35,7 @@ def build_parser():
     p.add_argument('--step', type=str, default="3")
     p.add_argument('--stage', type=str, default="train")
     p.add_argument('--batch', type=int, default=256)       # additive
+    p.add_argument('--WavLM_model_path', type=str, required=False)     # additive: also run wav_to_wavlm
     return p
 
 
@@ -63,10 +68,14 @@ def main(argv=None):
     from .checkpoint import load_config
     args = build_parser().parse_args(argv)
     if args.step != "3":
-        raise SystemExit("only --step 3 (dataset_to_code) is implemented; steps 1/2/4 are BVH/audio/text "
-                         "preprocessing with third-party models, out of scope")
-    return dataset_to_code(args.save_dir, args.prefix, 240, args.VQVAE_model_path, load_config(args.config),
-                           gpu=args.gpu, batch=args.batch)
+        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm) is implemented; steps 1/2/4 are BVH cutting, "
+                         "vq-wav2vec and sentence embeddings, out of scope")
+    written = dataset_to_code(args.save_dir, args.prefix, 240, args.VQVAE_model_path, load_config(args.config),
+                              gpu=args.gpu, batch=args.batch)
+    if args.WavLM_model_path:
+        from .wavlm import wav_to_wavlm
+        wav_to_wavlm(args.save_dir, args.prefix, args.WavLM_model_path, gpu=args.gpu)
+    return written
 
 
 if __name__ == "__main__":

@@ -325,3 +325,89 @@ def make_pae_motion(T, seed, still=None):
         a, b = still
         sig[a:b] = sig[a]
     return mean + std * sig
+
+
+# ----------------------------------------------------------------------------------------------
+# WavLM (process/WavLM/WavLM.py): seeded weights with the reference's key names, and seeded audio
+# ----------------------------------------------------------------------------------------------
+def _wavlm_cfg(layers, dim, ffn, heads, conv):
+    return dict(extractor_mode="layer_norm", encoder_layers=layers, encoder_embed_dim=dim, encoder_ffn_embed_dim=ffn,
+                encoder_attention_heads=heads, activation_fn="gelu", layer_norm_first=True,
+                conv_feature_layers="[(%d,10,5)] + [(%d,3,2)] * 4 + [(%d,2,2)] * 2" % (conv, conv, conv), conv_bias=False,
+                normalize=True, conv_pos=128, conv_pos_groups=16, relative_position_embedding=True, num_buckets=320,
+                max_distance=800, gru_rel_pos=True)
+
+
+WAVLM_TINY = dict(_wavlm_cfg(2, 128, 256, 2, 64), conv_bias=True)      # every kernel path at the smallest widths
+WAVLM_WIDE = _wavlm_cfg(2, 1024, 4096, 16, 512)        # WavLM-Large's tile shapes, two blocks
+WAVLM_LARGE = _wavlm_cfg(24, 1024, 4096, 16, 512)      # WavLM-Large.pt's cfg
+
+
+def make_wavlm_state_dict(seed, cfg=None):
+    """No WavLM checkpoint ships with the reference.  Seeded weights with the key names and shapes of the reference's
+    WavLM(cfg).state_dict() (`cfg` a dict in the checkpoint's form, default WAVLM_TINY).  Biases, LayerNorm weights, the
+    weight-norm gains and grep_a are non-trivial; the scales keep activations O(1) through every block."""
+    from .wavlm import conv_layers_of
+    cfg = dict(WAVLM_TINY if cfg is None else cfg)
+    rng = _rng(seed)
+    D, F, H = cfg["encoder_embed_dim"], cfg["encoder_ffn_embed_dim"], cfg["encoder_attention_heads"]
+    sd = {}
+
+    def f32(a):
+        return np.ascontiguousarray(a, np.float32)
+
+    def vec(name, n, scale=0.1):
+        sd[name] = f32(rng.standard_normal(n) * scale)
+
+    def norm(name, n):
+        sd[name + ".weight"] = f32(rng.uniform(0.6, 1.4, n))
+        vec(name + ".bias", n)
+
+    def linear(name, nout, nin, gain=1.0):
+        sd[name + ".weight"] = f32(rng.standard_normal((nout, nin)) * gain / np.sqrt(nin))
+        vec(name + ".bias", nout)
+
+    sd["mask_emb"] = f32(rng.uniform(0.0, 1.0, D))
+    cin = 1
+    for i, (c, k, s) in enumerate(conv_layers_of(cfg)):
+        sd["feature_extractor.conv_layers.%d.0.weight" % i] = f32(rng.standard_normal((c, cin, k)) * 1.4 / np.sqrt(cin * k))
+        if cfg.get("conv_bias", False):
+            vec("feature_extractor.conv_layers.%d.0.bias" % i, c)
+        norm("feature_extractor.conv_layers.%d.2.1" % i, c)
+        cin = c
+    if cin != D:
+        linear("post_extract_proj", D, cin)
+    K, G = cfg.get("conv_pos", 128), cfg.get("conv_pos_groups", 16)
+    vec("encoder.pos_conv.0.bias", D)
+    sd["encoder.pos_conv.0.weight_g"] = f32(rng.uniform(0.5, 1.5, (1, 1, K)))
+    sd["encoder.pos_conv.0.weight_v"] = f32(rng.standard_normal((D, D // G, K)) * 0.05)
+    for i in range(cfg["encoder_layers"]):
+        p = "encoder.layers.%d." % i
+        sd[p + "self_attn.grep_a"] = f32(rng.uniform(0.5, 1.5, (1, H, 1, 1)))
+        if i == 0:
+            sd[p + "self_attn.relative_attention_bias.weight"] = f32(rng.standard_normal((cfg["num_buckets"], H)))
+        for n in ("k_proj", "v_proj", "q_proj"):
+            linear(p + "self_attn." + n, D, D, 1.5)
+        linear(p + "self_attn.out_proj", D, D)
+        linear(p + "self_attn.grep_linear", 8, D // H)
+        norm(p + "self_attn_layer_norm", D)
+        linear(p + "fc1", F, D)
+        linear(p + "fc2", D, F)
+        norm(p + "final_layer_norm", D)
+    norm("encoder.layer_norm", D)
+    norm("layer_norm", cin)
+    return sd
+
+
+def make_wav(seed, B, n):
+    """(B, n) f32 seeded audio at 16 kHz: a few harmonics under a slow envelope plus noise, peak around 0.3 - not
+    normalised, like the samples the reference feeds the model."""
+    rng = _rng(seed)
+    t = np.arange(n, dtype=np.float64)[None, :] / 16000.0
+    wav = np.zeros((B, n))
+    for _ in range(4):
+        f = rng.uniform(90.0, 1800.0, (B, 1))
+        wav += rng.uniform(0.02, 0.1, (B, 1)) * np.sin(2 * np.pi * (f * t + rng.uniform(0, 1, (B, 1))))
+    wav *= 0.6 + 0.4 * np.sin(2 * np.pi * (rng.uniform(1.0, 4.0, (B, 1)) * t + rng.uniform(0, 1, (B, 1))))
+    wav += rng.standard_normal((B, n)) * 0.02
+    return np.ascontiguousarray(wav, np.float32)
