@@ -7,8 +7,8 @@
 // scipy's from_matrix orthogonalises a non-orthogonal input (the decoder's matrices are only approximately rotations)
 // by the orthogonal-Procrustes solution U V^T of its SVD and rejects non-positive determinants; U V^T is the orthogonal
 // polar factor, computed here by the Newton iteration X <- (X + X^-T)/2 (quadratically convergent, f64).  The Euler
-// angles are the closed form of R = Rz(a) Rx(b) Ry(c); at gimbal lock (|b| = 90 deg) the third angle is set to 0 like
-// scipy does.  One thread per (frame, joint); everything in f64.
+// angles are the closed form of R = Rz(a) Rx(b) Ry(c), b = atan2(sin b, cos b) with cos b = |(R20, R22)|; at gimbal
+// lock (|b| = 90 deg) the third angle is set to 0 like scipy does.  One thread per (frame, joint); everything in f64.
 #include "qpg_common.h"
 
 __global__ __launch_bounds__(256) void pose_to_euler_kernel(const float* __restrict__ poses, int64_t T, int J,
@@ -88,14 +88,16 @@ __global__ __launch_bounds__(256) void pose_to_euler_kernel(const float* __restr
   const double RAD = 57.29577951308232;
   double sb = x[7];
   sb = sb > 1.0 ? 1.0 : (sb < -1.0 ? -1.0 : sb);
-  const double b = asin(sb);
-  double a, c;
+  double a, b, c;
   if (fabs(sb) < 1.0 - 1e-14) {
     a = atan2(-x[1], x[4]);
     c = atan2(-x[6], x[8]);
+    // cos b from the row that carries it: asin(sb) alone loses b next to the lock (one ulp of sb = 1 - 1e-10 is 8e-12 rad)
+    b = atan2(sb, sqrt(x[6] * x[6] + x[8] * x[8]));
   } else {                                 // gimbal lock: only a +- c is defined; scipy sets the third angle to 0
     c = 0.0;
     a = atan2(x[3], x[0]);
+    b = asin(sb);
   }
   euler[i * 3 + 0] = a * RAD;
   euler[i * 3 + 1] = b * RAD;
