@@ -21,25 +21,36 @@ import torch
 
 from . import _lib
 
-IN_CH, MID_CH, EMBED, TIME, KEYS, WINDOW = 135, 15, 8, 240, 13, 4.0
-HALO, WS_STRIDE, MAX_CHUNK = 120, 136, 1 << 22
-OFF = dict(W1=0, BN1=522240, W2=522288, BN2=583728, FC=583776, FCBN=587616, FREQ=587664, TPI=587784)
-PARAM_FLOATS = 587792
+# Model(135, 8, 240, 13, 4.0): the dimensions and the layout of qpg_pae_phase_f32's buffers are include/qpg.h's
+IN_CH, MID_CH, EMBED, TIME = _lib.QPG_PAE_CHANNELS, _lib.QPG_PAE_MID, _lib.QPG_PAE_EMBED, _lib.QPG_PAE_TIME
+KEYS, WINDOW = 13, 4.0
+HALO, WS_STRIDE, MAX_CHUNK = _lib.QPG_PAE_HALO, _lib.QPG_PAE_WS_STRIDE, _lib.QPG_PAE_MAX_CHUNK
+OFF = {k[len("QPG_PAE_OFF_"):]: v for k, v in _lib.CONSTANTS.items() if k.startswith("QPG_PAE_OFF_")}
+PARAM_FLOATS = _lib.QPG_PAE_PARAM_FLOATS
 BN_EPS = 1e-5
 
 
-def _shapes():
-    s = {"tpi": (1,), "freqs": (TIME // 2,), "conv1.weight": (MID_CH, IN_CH, TIME), "conv1.bias": (MID_CH,),
-         "conv2.weight": (EMBED, MID_CH, TIME), "conv2.bias": (EMBED,)}
-    for name, n in (("bn_conv1", MID_CH), ("bn_conv2", EMBED)) + tuple(("bn.%d" % e, 2) for e in range(EMBED)):
-        for p in ("weight", "bias", "running_mean", "running_var"):
-            s[name + "." + p] = (n,)
-    for e in range(EMBED):
-        s["fc.%d.weight" % e], s["fc.%d.bias" % e] = (2, TIME), (2,)
+def param_specs():
+    """(name, shape) of every parameter in named_parameters() order (tpi, args, freqs first: not trainable)."""
+    s = [("tpi", (1,)), ("args", (TIME,)), ("freqs", (TIME // 2,)),
+         ("conv1.weight", (MID_CH, IN_CH, TIME)), ("conv1.bias", (MID_CH,)),
+         ("bn_conv1.weight", (MID_CH,)), ("bn_conv1.bias", (MID_CH,)),
+         ("conv2.weight", (EMBED, MID_CH, TIME)), ("conv2.bias", (EMBED,)),
+         ("bn_conv2.weight", (EMBED,)), ("bn_conv2.bias", (EMBED,))]
+    s += [x for e in range(EMBED) for x in (("fc.%d.weight" % e, (2, TIME)), ("fc.%d.bias" % e, (2,)))]
+    s += [x for e in range(EMBED) for x in (("bn.%d.weight" % e, (2,)), ("bn.%d.bias" % e, (2,)))]
+    s += [("deconv1.weight", (MID_CH, EMBED, TIME)), ("deconv1.bias", (MID_CH,)),
+          ("bn_deconv1.weight", (MID_CH,)), ("bn_deconv1.bias", (MID_CH,)),
+          ("deconv2.weight", (IN_CH, MID_CH, TIME)), ("deconv2.bias", (IN_CH,))]
     return s
 
 
-REQUIRED = _shapes()        # what phase extraction reads from a checkpoint (the deconv* half is ignored)
+PARAMS = param_specs()
+BN_LAYERS = [("bn_conv1", MID_CH), ("bn_conv2", EMBED)] + [("bn.%d" % e, 2) for e in range(EMBED)] + \
+    [("bn_deconv1", MID_CH)]
+STATS = [(bn + "." + k, (n,)) for bn, n in BN_LAYERS for k in ("running_mean", "running_var")]     # the buffers
+# what phase extraction reads from a checkpoint: the encoder half (no `args`, the deconv* half is ignored)
+REQUIRED = {k: shape for k, shape in PARAMS + STATS if k != "args" and "deconv" not in k}
 
 
 def bn_fold(sd, name):
@@ -77,9 +88,9 @@ def pack_params(sd):
     return P
 
 
-def state_dict_from(obj):
-    """A checkpoint path, a loaded checkpoint dict or a state dict -> {name: f32/f64 numpy} without `module.`;
-    refuses a missing key or a wrong shape."""
+def state_dict_from(obj, shapes=REQUIRED):
+    """A checkpoint path, a loaded checkpoint dict or a state dict -> {name: numpy} without `module.`; refuses a key of
+    `shapes` ({name: shape}) that is missing or has another shape."""
     if isinstance(obj, (str, os.PathLike)):
         from .checkpoint import load_checkpoint
         obj = load_checkpoint(obj)
@@ -89,11 +100,11 @@ def state_dict_from(obj):
     for k, v in obj.items():
         k = k[len("module."):] if k.startswith("module.") else k
         sd[k] = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-    missing = sorted(k for k in REQUIRED if k not in sd)
+    missing = sorted(k for k in shapes if k not in sd)
     if missing:
         raise ValueError("PAE checkpoint lacks %s" % ", ".join(missing))
-    for k, shape in REQUIRED.items():
-        if tuple(sd[k].shape) != shape:
+    for k, shape in shapes.items():
+        if tuple(sd[k].shape) != tuple(shape):
             raise ValueError("PAE checkpoint: %s has shape %s, expected %s" % (k, tuple(sd[k].shape), shape))
     return sd
 

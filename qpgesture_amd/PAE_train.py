@@ -23,29 +23,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from .PAE import (EMBED, IN_CH, KEYS, MID_CH, PARAMS, STATS, TIME, WINDOW, build_parser as pae_parser,
+                  state_dict_from)
 
-IN_CH, MID_CH, EMBED, TIME, KEYS, WINDOW = 135, 15, 8, 240, 13, 4.0
 LOSS_WEIGHT = 300.0
 LR, WEIGHT_DECAY, BETAS, EPS = 1e-4, 1e-4, (0.9, 0.999), 1e-8
 RESTART_PERIOD, T_MULT, MIN_LR = 10, 2, 1e-7
 SEED = 23456
 PAE_DEFAULTS = dict(epochs=100, save_per_epochs=10, n_poses=240, subdivision_stride=1,
                     model_save_path="./output/train_PAE", name="PAE")
-
-
-def param_specs():
-    """(name, shape) of every parameter in named_parameters() order (tpi, args, freqs first: not trainable)."""
-    s = [("tpi", (1,)), ("args", (TIME,)), ("freqs", (TIME // 2,)),
-         ("conv1.weight", (MID_CH, IN_CH, TIME)), ("conv1.bias", (MID_CH,)),
-         ("bn_conv1.weight", (MID_CH,)), ("bn_conv1.bias", (MID_CH,)),
-         ("conv2.weight", (EMBED, MID_CH, TIME)), ("conv2.bias", (EMBED,)),
-         ("bn_conv2.weight", (EMBED,)), ("bn_conv2.bias", (EMBED,))]
-    s += [x for e in range(EMBED) for x in (("fc.%d.weight" % e, (2, TIME)), ("fc.%d.bias" % e, (2,)))]
-    s += [x for e in range(EMBED) for x in (("bn.%d.weight" % e, (2,)), ("bn.%d.bias" % e, (2,)))]
-    s += [("deconv1.weight", (MID_CH, EMBED, TIME)), ("deconv1.bias", (MID_CH,)),
-          ("bn_deconv1.weight", (MID_CH,)), ("bn_deconv1.bias", (MID_CH,)),
-          ("deconv2.weight", (IN_CH, MID_CH, TIME)), ("deconv2.bias", (IN_CH,))]
-    return s
 
 
 def _offsets(specs):
@@ -56,12 +42,8 @@ def _offsets(specs):
     return off, o
 
 
-PARAMS = param_specs()
 OFF, PARAM_FLOATS = _offsets(PARAMS)
 TRAINABLE = OFF["conv1.weight"]                                   # QPG_PAET_TRAINABLE
-BN_LAYERS = [("bn_conv1", MID_CH), ("bn_conv2", EMBED)] + [("bn.%d" % e, 2) for e in range(EMBED)] + \
-    [("bn_deconv1", MID_CH)]
-STATS = [(bn + "." + k, (n,)) for bn, n in BN_LAYERS for k in ("running_mean", "running_var")]
 ST_OFF, STATS_FLOATS = _offsets(STATS)
 
 
@@ -119,18 +101,12 @@ def init_state_dict(seed=SEED):
 def pack(sd):
     """State dict (keys with or without `module.`) -> (params f32 [PARAM_FLOATS], stats f32 [STATS_FLOATS],
     num_batches_tracked); refuses a missing key or a wrong shape."""
-    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+    sd = state_dict_from(sd, dict(PARAMS + STATS))
     P, S = np.zeros(PARAM_FLOATS, np.float32), np.zeros(STATS_FLOATS, np.float32)
     for table, out, offs in ((PARAMS, P, OFF), (STATS, S, ST_OFF)):
-        for n, shape in table:
-            if n not in sd:
-                raise ValueError("PAE state dict lacks %s" % n)
-            v = sd[n].detach().cpu().numpy() if isinstance(sd[n], torch.Tensor) else np.asarray(sd[n])
-            if tuple(v.shape) != tuple(shape):
-                raise ValueError("PAE state dict: %s has shape %s, expected %s" % (n, tuple(v.shape), shape))
-            out[offs[n]:offs[n] + v.size] = v.reshape(-1)
-    nbt = sd.get("bn_conv1.num_batches_tracked", 0)
-    return P, S, int(nbt.item() if isinstance(nbt, torch.Tensor) else np.asarray(nbt))
+        for n, _ in table:
+            out[offs[n]:offs[n] + sd[n].size] = sd[n].reshape(-1)
+    return P, S, int(sd.get("bn_conv1.num_batches_tracked", 0))
 
 
 def unpack(P, S, nbt):
@@ -419,7 +395,6 @@ def train(args, cfg):
 
 
 def build_parser():
-    from .PAE import build_parser as pae_parser
     p = pae_parser()
     p.description = "PAE training"
     # additive

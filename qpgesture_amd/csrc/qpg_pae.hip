@@ -18,12 +18,15 @@
 //      99 348 MFMAs per frame, against 43 199 x 135 x 15 useful MACs (88 %).  Wave w owns tiles w, w+4, w+8, w+12
 //      (732, 732, 732, 726 tile-taps: balanced).  Epilogue: (acc + bias) * alpha + beta (eval BN), tanh, into LDS;
 //   3. conv2 the same way on the LDS image of conv1's output (15 tiles of 16 positions, k = (tap, 4 channels));
-//   4. DFT (f64 accumulation, twiddles from sincospi), f / a / b, the 8 fc layers (f64 dot products) and atan2'.
+//   4. the spectrum head of qpg_pae_model.h (shared with training): DFT (f64 accumulation), f / a / b, the 8 fc layers
+//      (f64 dot products, then the folded eval BN in f64) and atan2'.
 // Nothing in a frame's arithmetic depends on the batch, the chunk or the clip offset it comes in (the window is staged
 // the same way and every sum runs in a fixed order): results are bit-identical however the frames are grouped.
-#include "qpg_common.h"
+#include "qpg_pae_model.h"
 
 namespace {
+
+using namespace pae;
 
 constexpr int C_IN = QPG_PAE_CHANNELS;      // 135
 constexpr int CG1 = 34;                     // groups of 4 input channels (136)
@@ -65,9 +68,24 @@ __global__ __launch_bounds__(256) void pae_vel_kernel(const double* __restrict__
   ws[e] = v;
 }
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+// pae_phase_kernel writes its tap limits as literals: tile_ranges' general form costs the kernel about 75 scalar
+// instructions per block ahead of the tap loop, which showed as 0.3 % of its time.  They are tile_ranges' all the same:
+// conv1 is 241 positions x 240 taps over the 239 live window rows 1..239 (row 0 is zero) behind a pad of 121, with no
+// empty tile, so its loop runs from the least lo to the greatest hi; conv2 is 240 x 240 over y1's 241 positions behind
+// a pad of 119.
+constexpr bool tap_limits_are_tile_ranges() {
+  for (int w = 0; w < 4; ++w) {
+    const TileRange c1 = tile_ranges(w, TAPS + 1, TAPS, HALO + 1, TAPS - 1);
+    const TileRange c2 = tile_ranges(w, TAPS, TAPS, HALO - 1, TAPS + 1);
+    for (int j = 0; j < 4; ++j) {
+      const int t0 = 16 * (w + 4 * j);
+      if (c1.lo[j] != imax(0, 106 - t0) || c1.hi[j] != imin(TAPS - 1, 359 - t0) || c1.lo[j] > c1.hi[j]) return false;
+      if (c2.lo[j] != imax(0, 104 - t0) || c2.hi[j] != (t0 < TAPS ? imin(TAPS - 1, 359 - t0) : -1)) return false;
+    }
+  }
+  return true;
 }
+static_assert(tap_limits_are_tile_ranges(), "pae_phase_kernel's literal tap limits no longer match tile_ranges");
 
 __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict__ P, const int64_t* __restrict__ off,
                                                         int n_clips, int64_t frame0, const float* __restrict__ ws,
@@ -101,7 +119,7 @@ __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict_
   for (int j = 0; j < 4; ++j) {
     const int t0 = 16 * (w + 4 * j);
     acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    klo[j] = max(0, 106 - t0);
+    klo[j] = max(0, 106 - t0);              // (tap_limits_are_tile_ranges)
     khi[j] = min(TAPS - 1, 359 - t0);
   }
   const int kbeg = min(min(klo[0], klo[1]), min(klo[2], klo[3]));
@@ -131,8 +149,8 @@ __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict_
   float* y1 = lds;                          // [16][LS]
   float* lat = lds + 16 * LS;               // [8][240]
   double* tw = reinterpret_cast<double*>(lat + E * TAPS);      // [240][2] cos, sin of 2 pi n / 240
-  double* pw = tw + 2 * TAPS;               // [8][121] |X_m|^2 (m >= 1), pw[e][0] = Re X_0
-  float* vb = reinterpret_cast<float*>(pw + E * 121);          // [8][2] v
+  double* pw = tw + 2 * TAPS;               // [8][NB] |X_m|^2 (m >= 1), pw[e][0] = Re X_0
+  float* vb = reinterpret_cast<float*>(pw + E * NB);           // [8][2] v
   for (int e = tid; e < 16 * LS; e += 256) y1[e] = 0.0f;
   __syncthreads();
   {
@@ -140,17 +158,17 @@ __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict_
     const float bias = s1[r], alpha = s1[16 + r], beta = s1[32 + r];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int t0 = 16 * (w + 4 * j);
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        const int t = t0 + 4 * h + g4;      // C/D: column = lane & 15 (channel), row = 4 (lane >> 4) + register
+        const int t = tile_row(w, j, lane, g4);                // (the column, lane & 15 = r, is the channel)
         if (t <= TAPS && r < QPG_PAE_MID) y1[r * LS + t + LO] = tanhf(f_add(f_mul(f_add(acc[j][g4], bias), alpha), beta));
       }
     }
   }
   __syncthreads();
 
-  // ---- 3. conv2: tile m = w + 4 j covers u0 = 16 m; lane reads y1 channel 4 og + h at position u0 + r + k - 119
+  // ---- 3. conv2: tile m = w + 4 j covers u0 = 16 m (tile 15 does not exist: 240 positions); lane reads y1 channel
+  // 4 og + h at position u0 + r + k - 119
   {
     const float* W2 = P + QPG_PAE_OFF_W2;
     f32x4 a2[4];
@@ -159,8 +177,8 @@ __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict_
     for (int j = 0; j < 4; ++j) {
       const int u0 = 16 * (w + 4 * j);
       a2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      lo2[j] = max(0, 104 - u0);
-      hi2[j] = u0 < TAPS ? min(TAPS - 1, 359 - u0) : -1;      // (tile 15 does not exist: 240 positions)
+      lo2[j] = max(0, 104 - u0);            // (tap_limits_are_tile_ranges)
+      hi2[j] = u0 < TAPS ? min(TAPS - 1, 359 - u0) : -1;
     }
     for (int k = 0; k < TAPS; ++k) {
       float b[4];
@@ -180,75 +198,40 @@ __global__ __launch_bounds__(256) void pae_phase_kernel(const float* __restrict_
     const float bias = s2[r], alpha = s2[16 + r], beta = s2[32 + r];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int u0 = 16 * (w + 4 * j);
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        const int u = u0 + 4 * h + g4;
+        const int u = tile_row(w, j, lane, g4);
         if (u < TAPS && r < E) lat[r * TAPS + u] = tanhf(f_add(f_mul(f_add(a2[j][g4], bias), alpha), beta));
       }
     }
   }
-  for (int n = tid; n < TAPS; n += 256) {
-    double sn, cs;
-    sincospi((double)n / 120.0, &sn, &cs);
-    tw[2 * n] = cs;
-    tw[2 * n + 1] = sn;
-  }
+  fill_twiddles(tw, tid);
   __syncthreads();
 
-  // ---- 4. DFT of each latent channel (bins 0..120), f64 sums in u order
-  for (int task = tid; task < E * 121; task += 256) {
-    const int e = task / 121, m = task - e * 121;
-    const float* y = lat + e * TAPS;
-    double re = 0.0, im = 0.0;
-    int idx = 0;
-    for (int u = 0; u < TAPS; ++u) {
-      const double yu = (double)y[u];
-      re = f_add(re, f_mul(yu, tw[2 * idx]));
-      im = f_sub(im, f_mul(yu, tw[2 * idx + 1]));
-      idx += m;
-      if (idx >= TAPS) idx -= TAPS;
-    }
-    pw[e * 121 + m] = m == 0 ? re : f_add(f_mul(re, re), f_mul(im, im));
+  // ---- 4. DFT of each latent channel (bins 0..120)
+  for (int task = tid; task < E * NB; task += 256) {
+    const int e = task / NB, m = task - e * NB;
+    double re, im;
+    dft_bin(lat + e * TAPS, tw, m, re, im);
+    pw[task] = m == 0 ? re : bin_power(re, im);
   }
-  // the 8 fc layers: v[e][j] = BN(fc_e(latent_e))_j (f64 dot product, rounded to f32 like the reference's tensor)
+  // the 8 fc layers: v[e][j] = BN(fc_e(latent_e))_j (eval BN folded, in f64; rounded to f32 like the reference's tensor)
   if (tid < 2 * E) {
-    const int e = tid >> 1, jj = tid & 1;
-    const float* wf = P + QPG_PAE_OFF_FC + (e * 2 + jj) * TAPS;
-    const float* y = lat + e * TAPS;
-    double s = 0.0;
-    for (int u = 0; u < TAPS; ++u) s = f_add(s, f_mul((double)wf[u], (double)y[u]));
+    const int o = tid, e = o >> 1;
+    const double s = fc_dot(P + QPG_PAE_OFF_FC + o * TAPS, lat + e * TAPS);
     const float* fb = P + QPG_PAE_OFF_FCBN;
-    const int o = e * 2 + jj;
-    const double v = f_add(f_mul(f_add(s, (double)fb[o]), (double)fb[16 + o]), (double)fb[32 + o]);
-    vb[o] = (float)v;
+    vb[o] = (float)f_add(f_mul(f_add(s, (double)fb[o]), (double)fb[16 + o]), (double)fb[32 + o]);
   }
   __syncthreads();
 
   if (tid < E) {
     const int e = tid;
-    const float* fr = P + QPG_PAE_OFF_FREQ;
-    double sp = 0.0, sfp = 0.0;
-    for (int m = 1; m <= 120; ++m) {
-      const double p = pw[e * 121 + m];
-      sp = f_add(sp, p);
-      sfp = f_add(sfp, f_mul((double)fr[m - 1], p));
-    }
-    const double time_scale = 13.0 / 240.0;
-    const float f = (float)f_div(f_div(sfp, sp), time_scale);
-    const float a = (float)f_div(f_mul(2.0, sqrt(sp)), (double)TAPS);
-    const float b = (float)f_div(pw[e * 121], (double)TAPS);
-    // the model's own atan2 (PAE.py:103-108): atan(y / x), +- tpi / 2 where x < 0; NaN at (0, 0), +-pi/2 at x = 0
-    const float tpi = P[QPG_PAE_OFF_TPI];
-    const float x = vb[2 * e], y = vb[2 * e + 1];
-    float ang = atanf(f_div(y, x));
-    if (x < 0.0f && y >= 0.0f) ang = f_add(ang, f_mul(0.5f, tpi));
-    if (x < 0.0f && y < 0.0f) ang = f_sub(ang, f_mul(0.5f, tpi));
+    double sp, sfp;
+    power_sums(P + QPG_PAE_OFF_FREQ, [&](int m) { return pw[e * NB + m]; }, sp, sfp);
     float* o = out + gl * (4 * E);
-    o[e] = f_div(ang, tpi);
-    o[E + e] = f;
-    o[2 * E + e] = a;
-    o[3 * E + e] = b;
+    spectrum_fab(sp, sfp, pw[e * NB], o[E + e], o[2 * E + e], o[3 * E + e]);
+    const float x = vb[2 * e], y = vb[2 * e + 1];
+    o[e] = phase_of(x, y, P[QPG_PAE_OFF_TPI]);
     if (v_out) {
       v_out[gl * 2 * E + 2 * e] = x;
       v_out[gl * 2 * E + 2 * e + 1] = y;

@@ -15,10 +15,13 @@
 //                 partial weight gradient of a slab of windows; wred_kernel adds the slabs in slab order.
 // A thread owns 4 rows (r, r + 64, r + 128, r + 192) x 4 output channels; the source rows and coefficients of 4 loop
 // indices are staged in LDS per pass.  Every statistic (BN, spectrum, fc, loss, bias gradients) is an f64 sum in a
-// fixed order: no atomics anywhere, so two runs of the same step are bit-identical.
-#include "qpg_common.h"
+// fixed order: no atomics anywhere, so two runs of the same step are bit-identical.  The tile geometry and the spectrum
+// head (DFT, f / a / b, fc dot product, atan2') are qpg_pae_model.h's, shared with phase extraction.
+#include "qpg_pae_model.h"
 
 namespace {
+
+using namespace pae;
 
 constexpr int C = QPG_PAE_CHANNELS;   // 135
 constexpr int M = QPG_PAE_MID;        // 15
@@ -26,45 +29,36 @@ constexpr int E = QPG_PAE_EMBED;      // 8
 constexpr int T = QPG_PAE_TIME;       // 240 (also the number of taps)
 constexpr int L1 = T + 1;             // conv1 output positions
 constexpr int L3 = T - 1;             // deconv1 output positions
-constexpr int NB = T / 2 + 1;         // rfft bins
 constexpr double BN_EPS = 1e-5;
 constexpr double MOMENTUM = 0.1;
-constexpr double TIME_SCALE = 13.0 / 240.0;
+
+// The layers, each stated once (offsets into the parameter / gradient block and the running statistics).
+// Conv: (B, Cin, Lin) -> (B, Cout, Lout), T taps behind `pad` zeros; w = weight (Cout, Cin, T), b = bias (Cout).
+struct Conv {
+  int w, b, Cin, Lin, Cout, Lout, pad;
+};
+constexpr Conv CONV1{QPG_PAET_OFF_CONV1_W, QPG_PAET_OFF_CONV1_B, C, T, M, L1, T / 2};
+constexpr Conv CONV2{QPG_PAET_OFF_CONV2_W, QPG_PAET_OFF_CONV2_B, M, L1, E, T, (T - 1) / 2};
+constexpr Conv DECONV1{QPG_PAET_OFF_DECONV1_W, QPG_PAET_OFF_DECONV1_B, E, T, M, L3, (T - 1) / 2};
+constexpr Conv DECONV2{QPG_PAET_OFF_DECONV2_W, QPG_PAET_OFF_DECONV2_B, M, L3, C, T, T / 2};
+
+constexpr int BN_SLOT = 32;           // doubles per BN layer in the workspace's st and bs: [Cch] | [Cch], Cch <= 16
+// Bn: BatchNorm over (B, Cch, L); p = weight (Cch) | bias (Cch) (the fc BNs: per e, weight (2) | bias (2)), st =
+// running_mean | running_var laid out like p, slot = its BN_SLOT of the workspace's st (mean | invstd) and bs
+// (dbeta | dgamma).
+struct Bn {
+  int p, st, Cch, L, slot;
+};
+constexpr Bn BN1{QPG_PAET_OFF_BN1, QPG_PAET_ST_BN1, M, L1, 0};
+constexpr Bn BN2{QPG_PAET_OFF_BN2, QPG_PAET_ST_BN2, E, T, 1};
+constexpr Bn FCBN{QPG_PAET_OFF_FCBN, QPG_PAET_ST_FCBN, 2 * E, 1, 2};
+constexpr Bn BN3{QPG_PAET_OFF_BN3, QPG_PAET_ST_BN3, M, L3, 3};
 
 constexpr int NCH = 4;                // loop indices staged per pass = the k of one MFMA
 constexpr int XS = 528;               // LDS source row stride: r + q < 512, + 16 so that the 4 rows of a fragment
                                       // (lanes h = 0..3) fall on disjoint banks
 constexpr int QL = 256;               // LDS coefficient rows (q)
 constexpr int CS = QL * 16 + 16;      // LDS coefficient block stride (floats), + 16 for the same reason
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// Row tiles of a wave and the q range each one meets: wave w owns the 16-row tiles r0 = 16 (w + 4 j), j = 0..3.
-// Source row i = r + q holds position i - pad (zero outside 0 .. Lin-1), so a tile only meets data for
-// q in [pad - r0 - 15, pad - r0 + Lin - 1]; the rest of 0 .. nq-1 is padding and skipped.  Tiles at or past the
-// row count get an empty range.
-struct TileRange {
-  int lo[4], hi[4], beg, end;
-};
-
-__device__ __forceinline__ TileRange tile_ranges(int w, int rows, int nq, int pad, int Lin) {
-  TileRange tr;
-  tr.beg = nq;
-  tr.end = -1;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int r0 = 16 * (w + 4 * j);
-    tr.lo[j] = max(0, pad - r0 - 15);
-    tr.hi[j] = r0 < rows ? min(nq - 1, pad - r0 + Lin - 1) : -1;
-    if (tr.lo[j] <= tr.hi[j]) {
-      tr.beg = min(tr.beg, tr.lo[j]);
-      tr.end = max(tr.end, tr.hi[j]);
-    }
-  }
-  return tr;
-}
 
 // One staged pass: acc[j][row r0 + r][col c] += sum over h < 4, q of xs[h][r0 + r + q] cs[h][q][c], as one
 // v_mfma_f32_16x16x4_f32 per (tile, q): A[r][h] = xs[h][r0 + r + q] (lane r = lane & 15, h = lane >> 4),
@@ -114,14 +108,14 @@ __global__ __launch_bounds__(256) void corr_kernel(const float* __restrict__ src
     __syncthreads();
     corr_stage(xs, cs, wv, lane, tr, acc);
   }
-  const int c = lane & 15, h = lane >> 4, o = o0 + c;
+  const int o = o0 + (lane & 15);
   if (o >= Cout) return;
   const float bo = bias ? bias[o] : 0.0f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int t = 16 * (wv + 4 * j) + 4 * h + g;      // C/D: row 4 (lane >> 4) + register, column lane & 15
+      const int t = tile_row(wv, j, lane, g);
       if (t < Lout) out[((int64_t)b * Cout + o) * Lout + t] = f_add(acc[j][g], bo);
     }
   }
@@ -157,13 +151,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ sr
     __syncthreads();
     corr_stage(xs, cs, wv, lane, tr, acc);
   }
-  const int c = lane & 15, h = lane >> 4, o = o0 + c;
+  const int o = o0 + (lane & 15);
   if (o >= Cout) return;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int k = 16 * (wv + 4 * j) + 4 * h + g;
+      const int k = tile_row(wv, j, lane, g);
       if (k < T) part[(((int64_t)s * Cout + o) * Cin + n) * T + k] = acc[j][g];
     }
   }
@@ -196,22 +190,36 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
   __syncthreads();
 }
 
-// BatchNorm statistics of channel c of z (B, Cch, L), one block per channel.  train: batch mean and biased variance
-// (f64 sums), running statistics updated (momentum 0.1, unbiased variance); eval: the running statistics.
-// st[c] = mean, st[Cch + c] = 1 / sqrt(var + eps) (f64).
+// BatchNorm statistics of channel c of Cch from s = sum x, ss = sum x^2 over its N values: st[c] = mean,
+// st[Cch + c] = 1 / sqrt(var + eps) (f64; what bn_xhat reads).  train: batch mean and clamped biased variance, running
+// statistics updated (momentum 0.1, unbiased variance); eval: the running statistics (s, ss unused).
+template <class Int>
+__device__ __forceinline__ void bn_statistics(int train, double s, double ss, Int N, float* rmean, float* rvar,
+                                              double* st, int Cch, int c) {
+  if (train) {
+    const double mean = s / (double)N;
+    const double var = fmax(f_sub(ss / (double)N, f_mul(mean, mean)), 0.0);
+    st[c] = mean;
+    st[Cch + c] = 1.0 / sqrt(f_add(var, BN_EPS));
+    *rmean = (float)f_add(f_mul(1.0 - MOMENTUM, (double)*rmean), f_mul(MOMENTUM, mean));
+    *rvar = (float)f_add(f_mul(1.0 - MOMENTUM, (double)*rvar), f_mul(MOMENTUM, var * (double)N / (double)(N - 1)));
+  } else {
+    st[c] = (double)*rmean;
+    st[Cch + c] = 1.0 / sqrt(f_add((double)*rvar, BN_EPS));
+  }
+}
+
+// BatchNorm statistics of channel c of z (B, Cch, L), one block per channel (f64 sums)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ z, int B, int Cch, int L, int train,
                                                        float* __restrict__ rmean, float* __restrict__ rvar,
                                                        double* __restrict__ st) {
   __shared__ double red[512];
   const int c = blockIdx.x, tid = threadIdx.x;
+  const int64_t N = (int64_t)B * L;
   if (!train) {
-    if (tid == 0) {
-      st[c] = (double)rmean[c];
-      st[Cch + c] = 1.0 / sqrt(f_add((double)rvar[c], BN_EPS));
-    }
+    if (tid == 0) bn_statistics(0, 0.0, 0.0, N, rmean + c, rvar + c, st, Cch, c);
     return;
   }
-  const int64_t N = (int64_t)B * L;
   double s = 0.0, ss = 0.0;
   for (int64_t e = tid; e < N; e += 256) {
     const int64_t b = e / L, t = e - b * L;
@@ -220,14 +228,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     ss = f_add(ss, f_mul(v, v));
   }
   block_sum2(s, ss, red);
-  if (tid == 0) {
-    const double mean = s / (double)N;
-    const double var = fmax(f_sub(ss / (double)N, f_mul(mean, mean)), 0.0);
-    st[c] = mean;
-    st[Cch + c] = 1.0 / sqrt(f_add(var, BN_EPS));
-    rmean[c] = (float)f_add(f_mul(1.0 - MOMENTUM, (double)rmean[c]), f_mul(MOMENTUM, mean));
-    rvar[c] = (float)f_add(f_mul(1.0 - MOMENTUM, (double)rvar[c]), f_mul(MOMENTUM, var * (double)N / (double)(N - 1)));
-  }
+  if (tid == 0) bn_statistics(1, s, ss, N, rmean + c, rvar + c, st, Cch, c);
 }
 
 __device__ __forceinline__ float bn_xhat(float z, const double* st, int Cch, int c) {
@@ -276,52 +277,29 @@ __global__ __launch_bounds__(256) void spectrum_kernel(const float* __restrict__
   __shared__ double pw[E * NB];
   const int b = blockIdx.x, tid = threadIdx.x;
   for (int e = tid; e < E * T; e += 256) lat[e] = h2[(int64_t)b * E * T + e];
-  for (int n = tid; n < T; n += 256) {
-    double sn, cs;
-    sincospi((double)n / 120.0, &sn, &cs);
-    tw[2 * n] = cs;
-    tw[2 * n + 1] = sn;
-  }
+  fill_twiddles(tw, tid);
   __syncthreads();
   for (int task = tid; task < E * NB; task += 256) {
     const int e = task / NB, m = task - e * NB;
-    const float* y = lat + e * T;
-    double re = 0.0, im = 0.0;
-    int idx = 0;
-    for (int u = 0; u < T; ++u) {
-      const double yu = (double)y[u];
-      re = f_add(re, f_mul(yu, tw[2 * idx]));
-      im = f_sub(im, f_mul(yu, tw[2 * idx + 1]));
-      idx += m;
-      if (idx >= T) idx -= T;
-    }
+    double re, im;
+    dft_bin(lat + e * T, tw, m, re, im);
     double* o = spec + (((int64_t)b * E + e) * NB + m) * 2;
     o[0] = re;
     o[1] = im;
-    pw[task] = m == 0 ? re : f_add(f_mul(re, re), f_mul(im, im));
+    pw[task] = m == 0 ? re : bin_power(re, im);
   }
   if (tid < 2 * E) {
     const int e = tid >> 1, j = tid & 1;
-    const float* wf = P + QPG_PAET_OFF_FC + e * (2 * T + 2) + j * T;
-    const float* y = lat + e * T;
-    double s = 0.0;
-    for (int u = 0; u < T; ++u) s = f_add(s, f_mul((double)wf[u], (double)y[u]));
-    v[b * 2 * E + tid] = (float)f_add(s, (double)P[QPG_PAET_OFF_FC + e * (2 * T + 2) + 2 * T + j]);
+    const float* fc = P + QPG_PAET_OFF_FC + e * (2 * T + 2);   // fc.e.weight (2, 240), fc.e.bias (2)
+    v[b * 2 * E + tid] = (float)f_add(fc_dot(fc + j * T, lat + e * T), (double)fc[2 * T + j]);
   }
   __syncthreads();
   if (tid < E) {
     const int e = tid;
-    const float* fr = P + QPG_PAET_OFF_FREQS;
-    double sp = 0.0, sfp = 0.0;
-    for (int m = 1; m < NB; ++m) {
-      const double p = pw[e * NB + m];
-      sp = f_add(sp, p);
-      sfp = f_add(sfp, f_mul((double)fr[m - 1], p));
-    }
+    double sp, sfp;
+    power_sums(P + QPG_PAET_OFF_FREQS, [&](int m) { return pw[e * NB + m]; }, sp, sfp);
     float* o = pfab + b * 4 * E;
-    o[E + e] = (float)f_div(f_div(sfp, sp), TIME_SCALE);
-    o[2 * E + e] = (float)f_div(f_mul(2.0, sqrt(sp)), (double)T);
-    o[3 * E + e] = (float)f_div(pw[e * NB], (double)T);
+    spectrum_fab(sp, sfp, pw[e * NB], o[E + e], o[2 * E + e], o[3 * E + e]);
   }
 }
 
@@ -334,24 +312,16 @@ __global__ __launch_bounds__(256) void fcbn_kernel(const float* __restrict__ v, 
   const int tid = threadIdx.x;
   if (tid < 2 * E) {
     const int q = tid, e = q >> 1, j = q & 1;
-    float* rm = stats + QPG_PAET_ST_FCBN + 4 * e + j;
-    float* rv = rm + 2;
+    float* rm = stats + FCBN.st + 4 * e + j;                   // bn.e: running_mean (2) | running_var (2)
+    double s = 0.0, ss = 0.0;
     if (train) {
-      double s = 0.0, ss = 0.0;
       for (int b = 0; b < B; ++b) {
         const double x = (double)v[b * 2 * E + q];
         s = f_add(s, x);
         ss = f_add(ss, f_mul(x, x));
       }
-      const double mean = s / (double)B, var = fmax(f_sub(ss / (double)B, f_mul(mean, mean)), 0.0);
-      st[q] = mean;
-      st[2 * E + q] = 1.0 / sqrt(f_add(var, BN_EPS));
-      *rm = (float)f_add(f_mul(1.0 - MOMENTUM, (double)*rm), f_mul(MOMENTUM, mean));
-      *rv = (float)f_add(f_mul(1.0 - MOMENTUM, (double)*rv), f_mul(MOMENTUM, var * (double)B / (double)(B - 1)));
-    } else {
-      st[q] = (double)*rm;
-      st[2 * E + q] = 1.0 / sqrt(f_add((double)*rv, BN_EPS));
     }
+    bn_statistics(train, s, ss, B, rm, rm + 2, st, 2 * E, q);
   }
   __syncthreads();
   const float tpi = P[QPG_PAET_OFF_TPI];
@@ -360,15 +330,11 @@ __global__ __launch_bounds__(256) void fcbn_kernel(const float* __restrict__ v, 
     float xy[2];
     for (int j = 0; j < 2; ++j) {
       const int q = 2 * k + j;
-      const float* g = P + QPG_PAET_OFF_FCBN + 4 * k;
+      const float* g = P + FCBN.p + 4 * k;                     // bn.k: weight (2) | bias (2)
       xy[j] = f_add(f_mul(bn_xhat(v[b * 2 * E + q], st, 2 * E, q), g[j]), g[2 + j]);
       vn[b * 2 * E + q] = xy[j];
     }
-    const float x = xy[0], y = xy[1];
-    float ang = atanf(f_div(y, x));
-    if (x < 0.0f && y >= 0.0f) ang = f_add(ang, f_mul(0.5f, tpi));
-    if (x < 0.0f && y < 0.0f) ang = f_sub(ang, f_mul(0.5f, tpi));
-    pfab[b * 4 * E + k] = f_div(ang, tpi);
+    pfab[b * 4 * E + k] = phase_of(xy[0], xy[1], tpi);
   }
 }
 
@@ -458,7 +424,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
   }
 }
 
-// dz = gamma invstd (dA - dbeta / N - xhat dgamma / N)   (train-mode BatchNorm backward)
+// train-mode BatchNorm backward of one value: dz = gamma invstd (dA - dbeta / N - xhat dgamma / N)
+__device__ __forceinline__ float bn_bwd_term(double da, double xh, double dbeta, double dgamma, double N, double gamma,
+                                             double invstd) {
+  const double r = f_sub(f_sub(da, dbeta / N), f_mul(xh, dgamma / N));
+  return (float)f_mul(f_mul(gamma, invstd), r);
+}
+
+// tanh' and BatchNorm backward, apply half: dz from dA = dh (1 - h^2) and the sums of the reduction half
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ h,
                                                            const float* __restrict__ dh, int64_t n, int Cch, int L,
                                                            int64_t N, const double* __restrict__ st,
@@ -469,9 +442,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   const int c = (int)((e / L) % Cch);
   const float hv = h[e];
   const double da = (double)f_mul(dh[e], f_sub(1.0f, f_mul(hv, hv)));
-  const double xh = (double)bn_xhat(z[e], st, Cch, c);
-  const double r = f_sub(f_sub(da, bs[c] / (double)N), f_mul(xh, bs[Cch + c] / (double)N));
-  dz[e] = (float)f_mul(f_mul((double)gamma[c], st[Cch + c]), r);
+  dz[e] = bn_bwd_term(da, (double)bn_xhat(z[e], st, Cch, c), bs[c], bs[Cch + c], (double)N, (double)gamma[c],
+                      st[Cch + c]);
 }
 
 // signal backward and atan2' backward, one thread per (b, e): dfab[b][0..2][e] = df, da, db (f64 sums over t);
@@ -526,16 +498,14 @@ __global__ __launch_bounds__(256) void fcbn_bwd_kernel(const float* __restrict__
     }
     sums[q] = s0;
     sums[2 * E + q] = s1;
-    G[QPG_PAET_OFF_FCBN + 4 * e + j] = (float)s1;        // bn.e.weight
-    G[QPG_PAET_OFF_FCBN + 4 * e + 2 + j] = (float)s0;    // bn.e.bias
+    G[FCBN.p + 4 * e + j] = (float)s1;                         // bn.e.weight
+    G[FCBN.p + 4 * e + 2 + j] = (float)s0;                     // bn.e.bias
   }
   __syncthreads();
   for (int i = tid; i < B * 2 * E; i += 256) {
     const int q = i % (2 * E), k = q >> 1, j = q & 1;
-    const double gam = (double)P[QPG_PAET_OFF_FCBN + 4 * k + j];
-    const double xh = (double)bn_xhat(v[i], st, 2 * E, q);
-    const double r = f_sub(f_sub((double)dvn[i], sums[q] / (double)B), f_mul(xh, sums[2 * E + q] / (double)B));
-    dv[i] = (float)f_mul(f_mul(gam, st[2 * E + q]), r);
+    dv[i] = bn_bwd_term((double)dvn[i], (double)bn_xhat(v[i], st, 2 * E, q), sums[q], sums[2 * E + q], (double)B,
+                        (double)P[FCBN.p + 4 * k + j], st[2 * E + q]);
   }
   __syncthreads();
   if (tid < 2 * E) {
@@ -567,24 +537,14 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const double* __restric
   __shared__ double gm[E * NB];
   __shared__ double rei[E * NB * 2];
   const int b = blockIdx.x, tid = threadIdx.x;
-  for (int n = tid; n < T; n += 256) {
-    double sn, cs;
-    sincospi((double)n / 120.0, &sn, &cs);
-    tw[2 * n] = cs;
-    tw[2 * n + 1] = sn;
-  }
+  fill_twiddles(tw, tid);
   for (int i = tid; i < E * NB * 2; i += 256) rei[i] = spec[(int64_t)b * E * NB * 2 + i];
   __syncthreads();
   if (tid < E) {
     const int e = tid;
     const float* fr = P + QPG_PAET_OFF_FREQS;
-    double sp = 0.0, sfp = 0.0;
-    for (int m = 1; m < NB; ++m) {
-      const double re = rei[(e * NB + m) * 2], im = rei[(e * NB + m) * 2 + 1];
-      const double p = f_add(f_mul(re, re), f_mul(im, im));
-      sp = f_add(sp, p);
-      sfp = f_add(sfp, f_mul((double)fr[m - 1], p));
-    }
+    double sp, sfp;
+    power_sums(fr, [&](int m) { return bin_power(rei[(e * NB + m) * 2], rei[(e * NB + m) * 2 + 1]); }, sp, sfp);
     const double* d = dfab + (int64_t)b * 3 * E;
     const double df = d[e], da = d[E + e];
     const double fbar = sfp / sp;
@@ -654,8 +614,8 @@ Ws ws_layout(float* base, int B) {
   w.dh1 = f(b * M * L1); w.dz1 = f(b * M * L1); w.dv = f(b * 2 * E);   w.dvn = f(b * 2 * E);
   w.part = f((int64_t)n_slabs(B) * C * M * T);
   w.spec = d(b * E * NB * 2);
-  w.st = d(4 * 32);                          // per BN layer (conv1, conv2, fc, deconv1): [32] mean | invstd
-  w.bs = d(4 * 32);                          // backward sums per BN layer
+  w.st = d(4 * BN_SLOT);                     // per BN layer (Bn::slot): mean | invstd
+  w.bs = d(4 * BN_SLOT);                     // backward sums per BN layer
   w.dfab = d(b * 3 * E);
   w.lpart = d(loss_parts(B));
   w.loss = d(1);
@@ -665,45 +625,55 @@ Ws ws_layout(float* base, int B) {
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-int conv(hipStream_t s, const float* src, int B, int Cin, int Lin, const float* w, int flip, const float* bias, int Cout,
-         int Lout, int pad, float* out) {
-  hipLaunchKernelGGL(corr_kernel, dim3(B, (Cout + 15) / 16), dim3(256), 0, s, src, Cin, Lin, w, flip, bias, Cout, Lout,
-                     pad, out);
+// dgrad = 0: out = the convolution of src, + bias.  dgrad = 1: its data gradient, src = dL/d(output) -> out =
+// dL/d(input): the same correlation with the weights transposed and flipped behind T - 1 - pad zeros, no bias.
+int conv(hipStream_t s, const Conv& cv, int dgrad, const float* P, const float* src, int B, float* out) {
+  const Conv c = dgrad ? Conv{cv.w, cv.b, cv.Cout, cv.Lout, cv.Cin, cv.Lin, T - 1 - cv.pad} : cv;
+  hipLaunchKernelGGL(corr_kernel, dim3(B, (c.Cout + 15) / 16), dim3(256), 0, s, src, c.Cin, c.Lin, P + c.w, dgrad,
+                     dgrad ? nullptr : P + c.b, c.Cout, c.Lout, c.pad, out);
   QPG_LAUNCH_CHECK("corr_kernel");
   return QPG_OK;
 }
 
-int wgrad(hipStream_t s, const float* src, int B, int Cin, int Lin, const float* dy, int Cout, int Lout, int pad,
-          float* part, float* dw, float* db) {
+// weight and bias gradients of the convolution src -> dy into G
+int wgrad(hipStream_t s, const Conv& cv, const float* src, const float* dy, int B, float* part, float* G) {
   const int S = n_slabs(B);
-  hipLaunchKernelGGL(wgrad_kernel, dim3(Cin, (Cout + 15) / 16, S), dim3(256), 0, s, src, B, Cin, Lin, dy, Cout, Lout,
-                     pad, part);
+  hipLaunchKernelGGL(wgrad_kernel, dim3(cv.Cin, (cv.Cout + 15) / 16, S), dim3(256), 0, s, src, B, cv.Cin, cv.Lin, dy,
+                     cv.Cout, cv.Lout, cv.pad, part);
   QPG_LAUNCH_CHECK("wgrad_kernel");
-  const int64_t n = (int64_t)Cout * Cin * T;
-  hipLaunchKernelGGL(wred_kernel, dim3(nblk(n)), dim3(256), 0, s, part, S, n, dw);
+  const int64_t n = (int64_t)cv.Cout * cv.Cin * T;
+  hipLaunchKernelGGL(wred_kernel, dim3(nblk(n)), dim3(256), 0, s, part, S, n, G + cv.w);
   QPG_LAUNCH_CHECK("wred_kernel");
-  hipLaunchKernelGGL(chan_sum_kernel, dim3(Cout), dim3(256), 0, s, dy, B, Cout, Lout, db);
+  hipLaunchKernelGGL(chan_sum_kernel, dim3(cv.Cout), dim3(256), 0, s, dy, B, cv.Cout, cv.Lout, G + cv.b);
   QPG_LAUNCH_CHECK("chan_sum_kernel");
   return QPG_OK;
 }
 
-int bn_fwd(hipStream_t s, const float* z, int B, int Cch, int L, int train, float* rm, float* rv, double* st,
-           const float* gamma, const float* beta, float* h) {
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(Cch), dim3(256), 0, s, z, B, Cch, L, train, rm, rv, st);
+// h = tanh(BN(z)); S: the running statistics
+int bn_fwd(hipStream_t s, const Bn& bn, const Ws& w, const float* P, float* S, const float* z, int B, int train,
+           float* h) {
+  double* st = w.st + BN_SLOT * bn.slot;
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(bn.Cch), dim3(256), 0, s, z, B, bn.Cch, bn.L, train, S + bn.st,
+                     S + bn.st + bn.Cch, st);
   QPG_LAUNCH_CHECK("bn_stats_kernel");
-  const int64_t n = (int64_t)B * Cch * L;
-  hipLaunchKernelGGL(bn_tanh_kernel, dim3(nblk(n)), dim3(256), 0, s, z, n, Cch, L, st, gamma, beta, h);
+  const int64_t n = (int64_t)B * bn.Cch * bn.L;
+  hipLaunchKernelGGL(bn_tanh_kernel, dim3(nblk(n)), dim3(256), 0, s, z, n, bn.Cch, bn.L, st, P + bn.p,
+                     P + bn.p + bn.Cch, h);
   QPG_LAUNCH_CHECK("bn_tanh_kernel");
   return QPG_OK;
 }
 
-int bn_bwd(hipStream_t s, const float* z, const float* h, const float* dh, int B, int Cch, int L, const double* st,
-           double* bs, const float* gamma, float* dgamma, float* dbeta, float* dz) {
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(Cch), dim3(256), 0, s, z, h, dh, B, Cch, L, st, bs, dgamma, dbeta);
+// dz from dh through tanh and the train-mode BN; the BN's weight and bias gradients into G
+int bn_bwd(hipStream_t s, const Bn& bn, const Ws& w, const float* P, float* G, const float* z, const float* h,
+           const float* dh, int B, float* dz) {
+  const double* st = w.st + BN_SLOT * bn.slot;
+  double* bs = w.bs + BN_SLOT * bn.slot;
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(bn.Cch), dim3(256), 0, s, z, h, dh, B, bn.Cch, bn.L, st, bs, G + bn.p,
+                     G + bn.p + bn.Cch);
   QPG_LAUNCH_CHECK("bn_bwd_reduce_kernel");
-  const int64_t n = (int64_t)B * Cch * L;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(n)), dim3(256), 0, s, z, h, dh, n, Cch, L, (int64_t)B * L, st, bs,
-                     gamma, dz);
+  const int64_t n = (int64_t)B * bn.Cch * bn.L;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(n)), dim3(256), 0, s, z, h, dh, n, bn.Cch, bn.L,
+                     (int64_t)B * bn.L, st, bs, P + bn.p, dz);
   QPG_LAUNCH_CHECK("bn_bwd_apply_kernel");
   return QPG_OK;
 }
@@ -746,22 +716,19 @@ extern "C" int qpg_pae_train_forward_f32(qpg_ctx* ctx, void* stream, const float
   hipLaunchKernelGGL(gather_kernel, dim3(nblk((int64_t)B * C * T)), dim3(256), 0, s, poses, n_frames, starts, B, tr,
                      w.x0);
   QPG_LAUNCH_CHECK("gather_kernel");
-  QPG_TRY(conv(s, w.x0, B, C, T, P + QPG_PAET_OFF_CONV1_W, 0, P + QPG_PAET_OFF_CONV1_B, M, L1, T / 2, w.z1));
-  QPG_TRY(bn_fwd(s, w.z1, B, M, L1, tr, S + QPG_PAET_ST_BN1, S + QPG_PAET_ST_BN1 + M, w.st, P + QPG_PAET_OFF_BN1,
-                 P + QPG_PAET_OFF_BN1 + M, w.h1));
-  QPG_TRY(conv(s, w.h1, B, M, L1, P + QPG_PAET_OFF_CONV2_W, 0, P + QPG_PAET_OFF_CONV2_B, E, T, (T - 1) / 2, w.z2));
-  QPG_TRY(bn_fwd(s, w.z2, B, E, T, tr, S + QPG_PAET_ST_BN2, S + QPG_PAET_ST_BN2 + E, w.st + 32,
-                 P + QPG_PAET_OFF_BN2, P + QPG_PAET_OFF_BN2 + E, w.h2));
+  QPG_TRY(conv(s, CONV1, 0, P, w.x0, B, w.z1));
+  QPG_TRY(bn_fwd(s, BN1, w, P, S, w.z1, B, tr, w.h1));
+  QPG_TRY(conv(s, CONV2, 0, P, w.h1, B, w.z2));
+  QPG_TRY(bn_fwd(s, BN2, w, P, S, w.z2, B, tr, w.h2));
   hipLaunchKernelGGL(spectrum_kernel, dim3(B), dim3(256), 0, s, w.h2, P, w.spec, w.pfab, w.v);
   QPG_LAUNCH_CHECK("spectrum_kernel");
-  hipLaunchKernelGGL(fcbn_kernel, dim3(1), dim3(256), 0, s, w.v, B, tr, P, S, w.st + 64, w.vn, w.pfab);
+  hipLaunchKernelGGL(fcbn_kernel, dim3(1), dim3(256), 0, s, w.v, B, tr, P, S, w.st + BN_SLOT * FCBN.slot, w.vn, w.pfab);
   QPG_LAUNCH_CHECK("fcbn_kernel");
   hipLaunchKernelGGL(signal_kernel, dim3(nblk((int64_t)B * E * T)), dim3(256), 0, s, w.pfab, P, B, w.sig);
   QPG_LAUNCH_CHECK("signal_kernel");
-  QPG_TRY(conv(s, w.sig, B, E, T, P + QPG_PAET_OFF_DECONV1_W, 0, P + QPG_PAET_OFF_DECONV1_B, M, L3, (T - 1) / 2, w.z3));
-  QPG_TRY(bn_fwd(s, w.z3, B, M, L3, tr, S + QPG_PAET_ST_BN3, S + QPG_PAET_ST_BN3 + M, w.st + 96,
-                 P + QPG_PAET_OFF_BN3, P + QPG_PAET_OFF_BN3 + M, w.h3));
-  QPG_TRY(conv(s, w.h3, B, M, L3, P + QPG_PAET_OFF_DECONV2_W, 0, P + QPG_PAET_OFF_DECONV2_B, C, T, T / 2, w.y));
+  QPG_TRY(conv(s, DECONV1, 0, P, w.sig, B, w.z3));
+  QPG_TRY(bn_fwd(s, BN3, w, P, S, w.z3, B, tr, w.h3));
+  QPG_TRY(conv(s, DECONV2, 0, P, w.h3, B, w.y));
   const int64_t n = (int64_t)B * C * T;
   const float gscale = (float)(600.0 / (double)n);
   hipLaunchKernelGGL(loss_kernel, dim3((unsigned)loss_parts(B)), dim3(256), 0, s, w.y, w.x0, n, gscale,
@@ -788,33 +755,28 @@ extern "C" int qpg_pae_train_backward_f32(qpg_ctx* ctx, void* stream, const floa
   const float* P = params;
   float* G = grads;
   // deconv2 -> dh3 -> BN3 -> dz3
-  QPG_TRY(wgrad(s, w.h3, B, M, L3, w.dy, C, T, T / 2, w.part, G + QPG_PAET_OFF_DECONV2_W, G + QPG_PAET_OFF_DECONV2_B));
-  QPG_TRY(conv(s, w.dy, B, C, T, P + QPG_PAET_OFF_DECONV2_W, 1, nullptr, M, L3, T - 1 - T / 2, w.dh3));
-  QPG_TRY(bn_bwd(s, w.z3, w.h3, w.dh3, B, M, L3, w.st + 96, w.bs + 96, P + QPG_PAET_OFF_BN3,
-                 G + QPG_PAET_OFF_BN3, G + QPG_PAET_OFF_BN3 + M, w.dz3));
+  QPG_TRY(wgrad(s, DECONV2, w.h3, w.dy, B, w.part, G));
+  QPG_TRY(conv(s, DECONV2, 1, P, w.dy, B, w.dh3));
+  QPG_TRY(bn_bwd(s, BN3, w, P, G, w.z3, w.h3, w.dh3, B, w.dz3));
   // deconv1 -> ds
-  QPG_TRY(wgrad(s, w.sig, B, E, T, w.dz3, M, L3, (T - 1) / 2, w.part, G + QPG_PAET_OFF_DECONV1_W,
-                G + QPG_PAET_OFF_DECONV1_B));
-  QPG_TRY(conv(s, w.dz3, B, M, L3, P + QPG_PAET_OFF_DECONV1_W, 1, nullptr, E, T, T - 1 - (T - 1) / 2, w.ds));
+  QPG_TRY(wgrad(s, DECONV1, w.sig, w.dz3, B, w.part, G));
+  QPG_TRY(conv(s, DECONV1, 1, P, w.dz3, B, w.ds));
   // signal, atan2', fc BN, fc, spectrum -> dh2
   hipLaunchKernelGGL(signal_bwd_kernel, dim3(nblk((int64_t)B * E)), dim3(256), 0, s, w.ds, w.pfab, w.vn, P, B, w.dfab,
                      w.dvn);
   QPG_LAUNCH_CHECK("signal_bwd_kernel");
-  hipLaunchKernelGGL(fcbn_bwd_kernel, dim3(1), dim3(256), 0, s, w.v, w.dvn, B, w.st + 64, P, G, w.dv);
+  hipLaunchKernelGGL(fcbn_bwd_kernel, dim3(1), dim3(256), 0, s, w.v, w.dvn, B, w.st + BN_SLOT * FCBN.slot, P, G, w.dv);
   QPG_LAUNCH_CHECK("fcbn_bwd_kernel");
   hipLaunchKernelGGL(fc_wgrad_kernel, dim3(nblk(2 * E * T)), dim3(256), 0, s, w.dv, w.h2, B, G);
   QPG_LAUNCH_CHECK("fc_wgrad_kernel");
   hipLaunchKernelGGL(latent_bwd_kernel, dim3(B), dim3(256), 0, s, w.spec, w.dfab, w.dv, P, w.dh2);
   QPG_LAUNCH_CHECK("latent_bwd_kernel");
   // BN2 -> conv2 -> dh1 -> BN1 -> conv1
-  QPG_TRY(bn_bwd(s, w.z2, w.h2, w.dh2, B, E, T, w.st + 32, w.bs + 32, P + QPG_PAET_OFF_BN2, G + QPG_PAET_OFF_BN2,
-                 G + QPG_PAET_OFF_BN2 + E, w.dz2));
-  QPG_TRY(wgrad(s, w.h1, B, M, L1, w.dz2, E, T, (T - 1) / 2, w.part, G + QPG_PAET_OFF_CONV2_W,
-                G + QPG_PAET_OFF_CONV2_B));
-  QPG_TRY(conv(s, w.dz2, B, E, T, P + QPG_PAET_OFF_CONV2_W, 1, nullptr, M, L1, T - 1 - (T - 1) / 2, w.dh1));
-  QPG_TRY(bn_bwd(s, w.z1, w.h1, w.dh1, B, M, L1, w.st, w.bs, P + QPG_PAET_OFF_BN1, G + QPG_PAET_OFF_BN1,
-                 G + QPG_PAET_OFF_BN1 + M, w.dz1));
-  QPG_TRY(wgrad(s, w.x0, B, C, T, w.dz1, M, L1, T / 2, w.part, G + QPG_PAET_OFF_CONV1_W, G + QPG_PAET_OFF_CONV1_B));
+  QPG_TRY(bn_bwd(s, BN2, w, P, G, w.z2, w.h2, w.dh2, B, w.dz2));
+  QPG_TRY(wgrad(s, CONV2, w.h1, w.dz2, B, w.part, G));
+  QPG_TRY(conv(s, CONV2, 1, P, w.dz2, B, w.dh1));
+  QPG_TRY(bn_bwd(s, BN1, w, P, G, w.z1, w.h1, w.dh1, B, w.dz1));
+  QPG_TRY(wgrad(s, CONV1, w.x0, w.dz1, B, w.part, G));
   return QPG_OK;
 }
 
