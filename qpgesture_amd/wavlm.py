@@ -250,8 +250,12 @@ class WavLM:
     def _forward(self, source, on_stage=None):
         """The launches of one call.  on_stage(name, result), if given, is called at the stage boundaries with a view of
         the workspace: "start" (None), "features" (conv stack, [B][T][C]), "front_end" (after post_extract_proj),
-        "pos_conv" (x + GELU(pos_conv(x))), "block0" (the first block's output), "blocks" (the returned result).  The
-        tests copy the views, tools/bench_wavlm.py records a device event per stage."""
+        "pos_conv" (x + GELU(pos_conv(x))), "block0" (the first block's output), "blocks" (the returned result) - and
+        after every other launch with that launch's output: "conv<i>" / "conv<i>_norm" ([B][frames of layer i][C]),
+        "front_norm" (the layer_norm ahead of post_extract_proj), "pos_pad" ([B][G][T + taps - 1][D / G]) and, per
+        block, "block<i>.ln1", ".gate", ".qkv", ".att", ".out_proj", ".ln2", ".fc1", ".fc2".  A view is valid until the
+        next launch (LayerNorms and residual GEMMs run in place).  The tests copy the views, tools/bench_wavlm.py
+        records a device event per stage."""
         import torch
         from . import _lib
         wav = torch.as_tensor(source, dtype=torch.float32).to(self.device)
@@ -273,9 +277,10 @@ class WavLM:
         ws, p = self._workspace(B, n), self.p
         call = _lib.call
 
-        def mark(stage, flat=None, width=0):
+        def mark(stage, flat=None, width=0, rows=None):
             if on_stage is not None:
-                on_stage(stage, None if flat is None else flat[:B * T * width].view(B, T, width))
+                rows = T if rows is None else rows
+                on_stage(stage, None if flat is None else flat[:B * rows * width].view(B, rows, width))
 
         def gemm(A, lda, W, bias, res, out, ldc, M, N, K, gelu=0, n_outer=1, n_inner=1, a_outer=0, a_inner=0, w_inner=0,
                  bias_inner=0, c_outer=0, c_inner=0):
@@ -291,13 +296,17 @@ class WavLM:
         L0 = p["conv"][0]
         cur, nxt = ws["a"], ws["b"]
         call("qpg_wavlm_conv0_f32", dev, wav, B, n, L0["w"], L0["b"], C, k0, s0, cur)
+        mark("conv0", cur, C, fr[0])
         ln(cur, L0["g"], L0["beta"], B * fr[0], C, 1, cur)
+        mark("conv0_norm", cur, C, fr[0])
         for i in range(1, len(self.conv_layers)):
             _, k, s = self.conv_layers[i]
             L = p["conv"][i]
             gemm(cur, s * C, L["w"], L["b"], None, nxt, C, fr[i], C, k * C, n_outer=B, a_outer=fr[i - 1] * C,
                  c_outer=fr[i] * C)
+            mark("conv%d" % i, nxt, C, fr[i])
             ln(nxt, L["g"], L["beta"], B * fr[i], C, 1, nxt)
+            mark("conv%d_norm" % i, nxt, C, fr[i])
             cur, nxt = nxt, cur
         M = B * T
         mark("features", cur, C)
@@ -305,6 +314,7 @@ class WavLM:
         x, y, h = ws["x"], ws["y"], ws["h"]
         if p["proj_w"] is not None:
             ln(cur, p["ln_g"], p["ln_b"], M, C, 0, cur)
+            mark("front_norm", cur, C)
             gemm(cur, C, p["proj_w"], p["proj_b"], None, x, D, M, D, C)
         else:
             ln(cur, p["ln_g"], p["ln_b"], M, C, 0, x)
@@ -313,20 +323,31 @@ class WavLM:
         K, G = c.conv_pos, c.conv_pos_groups
         Cg, rows = D // G, T + c.conv_pos - 1
         call("qpg_wavlm_pos_pad_f32", dev, x, B, T, D, G, K, ws["pad"])
+        if on_stage is not None:
+            on_stage("pos_pad", ws["pad"][:B * rows * D].view(B, G, rows, Cg))
         gemm(ws["pad"], Cg, p["pos_w"], p["pos_b"], x, y, D, T, Cg, K * Cg, gelu=1, n_outer=B, n_inner=G,
              a_outer=G * rows * Cg, a_inner=rows * Cg, w_inner=Cg * K * Cg, bias_inner=Cg, c_outer=T * D, c_inner=Cg)
         x = y
         relb = self.position_bias_table(T)
         mark("pos_conv", x, D)
         for i, L in enumerate(p["layers"]):
+            blk = "block%d." % i
             ln(x, L["ln1_g"], L["ln1_b"], M, D, 0, h)
+            mark(blk + "ln1", h, D)
             call("qpg_wavlm_gate_f32", dev, h, L["grep_w"], L["grep_b"], L["grep_a"], M, H, ws["gate"])
+            mark(blk + "gate", ws["gate"], H)
             gemm(h, D, L["qkv_w"], L["qkv_b"], None, ws["qkv"], 3 * D, M, 3 * D, D)
+            mark(blk + "qkv", ws["qkv"], 3 * D)
             call("qpg_wavlm_attention_f32", dev, ws["qkv"], ws["gate"], relb, B, T, H, ws["att"])
+            mark(blk + "att", ws["att"], D)
             gemm(ws["att"], D, L["out_w"], L["out_b"], x, x, D, M, D, D)
+            mark(blk + "out_proj", x, D)
             ln(x, L["ln2_g"], L["ln2_b"], M, D, 0, h)
+            mark(blk + "ln2", h, D)
             gemm(h, D, L["fc1_w"], L["fc1_b"], None, ws["ffn"], F, M, F, D, gelu=1)
+            mark(blk + "fc1", ws["ffn"], F)
             gemm(ws["ffn"], F, L["fc2_w"], L["fc2_b"], x, x, D, M, D, F)
+            mark(blk + "fc2", x, D)
             if i == 0:
                 mark("block0", x, D)
         out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
