@@ -1007,6 +1007,22 @@ int qpg_wavlm_gate_f32(qpg_ctx*, void* stream, const float* x_ln, const float* g
 int qpg_wavlm_attention_f32(qpg_ctx*, void* stream, const float* qkv, const float* gate, const float* relb, int B, int T,
                             int H, float* out);
 
+/* x[m][0 .. C) = 0 for every row m < M with row_mask[m] != 0 ([dev] uint8 [M]); the other rows are not written.  The
+ * reference's `x[padding_mask] = 0` ahead of pos_conv (WavLM.py:574-575). */
+int qpg_wavlm_mask_rows_f32(qpg_ctx*, void* stream, float* x, const uint8_t* row_mask, int64_t M, int C);
+
+/* The same attention for long and for ragged inputs: the operands of qpg_wavlm_attention_f32 plus key_mask, [dev] uint8
+ * [B][T] (nonzero: the key is excluded for every query of its batch member) or NULL (no key excluded).  A block owns 128
+ * queries of one (batch, head) and walks the keys in tiles of 64: both products run on the f32 matrix cores, the softmax
+ * is online (running maximum; numerator and sum rescaled per key tile), and per tile pair only the 191 table entries it
+ * can address are staged, so neither LDS nor registers grow with T.  A masked key contributes nothing: the result is
+ * bit-identical whatever qkv holds at masked keys (NaN and Inf included).  Rows of masked QUERIES are computed like any
+ * other.  The caller guarantees at least one valid key per batch member (a member without one gets NaN rows).
+ * 1 <= T <= QPG_WAVLM_MAX_FRAMES_LONG, above it QPG_EUNSUP with nothing launched. */
+#define QPG_WAVLM_MAX_FRAMES_LONG 32768
+int qpg_wavlm_attention_tiled_f32(qpg_ctx*, void* stream, const float* qkv, const float* gate, const float* relb,
+                                  const uint8_t* key_mask, int B, int T, int H, float* out);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

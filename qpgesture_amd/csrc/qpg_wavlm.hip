@@ -18,6 +18,10 @@
 // wavlm_gate_kernel    the gated relative-position factor gate_a (gate_b grep_a[h] - 1) + 2 per (row, head);
 // wavlm_attn_kernel    one block per (batch, head, 16 queries): scores q k^T + gate * bias[k - q] from the [2T-1][H] table,
 //                      max-subtracted softmax in LDS, times V.  No (B H, T, T) array exists in memory.
+// wavlm_mask_rows_kernel   zeroes the rows a byte mask names (the padded frames of a ragged batch, ahead of pos_conv);
+// wavlm_attn_tiled_kernel  the same attention for any T and with a key mask: one block per (batch, head, 128 queries)
+//                      walks the keys in tiles of 64, K Q^T and V^T P^T on the f32 matrix cores, online softmax; LDS and
+//                      registers do not grow with T.
 #include "qpg_common.h"
 
 namespace {
@@ -361,6 +365,143 @@ __global__ __launch_bounds__(256) void wavlm_attn_kernel(const float* __restrict
   }
 }
 
+// ---- x[m][:] = 0 for the rows with row_mask[m] != 0 (the padded frames ahead of pos_conv); other rows are not written
+__global__ __launch_bounds__(256) void wavlm_mask_rows_kernel(float* __restrict__ x, const uint8_t* __restrict__ row_mask,
+                                                              int64_t total, int C) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  if (row_mask[e / C]) x[e] = 0.0f;
+}
+
+// ---- tiled attention: the operands of wavlm_attn_kernel plus key_mask [B][T] (nonzero: the key is excluded) or NULL.
+// A block owns LQ = 128 queries of one (batch, head), 32 per wave, and walks the keys in tiles of LK = 64.  Both products
+// are computed TRANSPOSED so that a query is a matrix-core COLUMN, i.e. one lane (and its partner lane + 32):
+//   S^T [key][query] = K [key][d] Q^T [d][query]      A = K from LDS, B = the wave's Q fragment, held in registers;
+//   O^T [d][query]   = V^T [d][key] P^T [key][query]  A = V from LDS, B = the S^T registers as they stand: register r of
+//                      a lane holds key (r & 3) + 8 (r >> 2) + 4 (lane >> 5), and step r of the second product takes
+//                      exactly that key pair, so P never travels through LDS.
+// The running maximum m, the running sum l and the rescale factor are therefore per-lane scalars.  Online softmax: per
+// key tile m' = max(m, tile max), alpha = exp(m - m'), l = l alpha + sum p, O = O alpha + P V; out = O / l at the end.
+// A masked key (and a key past T in the last tile) is staged as zeros and its weight is SELECTED to 0, its score to -inf
+// ahead of the maximum: nothing read from it reaches a result.  A tile without a valid key is skipped by the whole
+// block, so m is finite from the first tile that is not.  Per (query tile, key tile) the LQ + LK - 1 table entries
+// k - q in [k0 - q0 - (LQ - 1), k0 - q0 + LK - 1] are staged.
+constexpr int LQ = 128, LK = 64, KLD = HD + 1;
+
+__global__ __launch_bounds__(256) void wavlm_attn_tiled_kernel(const float* __restrict__ qkv, const float* __restrict__ gate,
+                                                               const float* __restrict__ relb,
+                                                               const uint8_t* __restrict__ key_mask, int T, int H,
+                                                               float* __restrict__ out) {
+  __shared__ float Ks[LK][KLD];
+  __shared__ __attribute__((aligned(16))) float Vs[LK][HD];
+  __shared__ float bs[LQ + LK];
+  __shared__ int vf[LK];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 31, lk = lane >> 5;
+  const int q0 = blockIdx.x * LQ, h = blockIdx.y, b = blockIdx.z;
+  const int D = H * HD;
+  const float* base = qkv + (int64_t)b * T * 3 * D + h * HD;
+  const uint8_t* km = key_mask ? key_mask + (int64_t)b * T : nullptr;
+  const int ql = w * 32 + lr, q = q0 + ql;
+  const bool qlive = q < T;
+
+  // the wave's Q^T fragment: lane (lr, lk) holds channels 32 lk .. 32 lk + 31 of query lr; step j of the first product
+  // pairs channel j (lanes < 32) with channel 32 + j (lanes >= 32)
+  f32x4 qf[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    qf[i] = qlive ? *reinterpret_cast<const f32x4*>(base + (int64_t)q * 3 * D + 32 * lk + 4 * i) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const float g = qlive ? gate[((int64_t)b * T + q) * H + h] : 0.0f;
+  float m = -INFINITY, l = 0.0f;
+  f32x16 acc[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[dt][r] = 0.0f;
+
+  const int sr = tid >> 2, skq = tid & 3;              // staging: thread (sr, skq) takes 16 channels of key k0 + sr
+  for (int k0 = 0; k0 < T; k0 += LK) {
+    __syncthreads();
+    const int key = k0 + sr;
+    const bool valid = key < T && !(km && km[key]);
+    const float* kp = base + (int64_t)min(key, T - 1) * 3 * D + D;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int d = skq * 4 + 16 * i;
+      f32x4 kv = {0.0f, 0.0f, 0.0f, 0.0f}, vv = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (valid) {
+        kv = *reinterpret_cast<const f32x4*>(kp + d);
+        vv = *reinterpret_cast<const f32x4*>(kp + D + d);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Ks[sr][d + j] = kv[j];
+      *reinterpret_cast<f32x4*>(&Vs[sr][d]) = vv;
+    }
+    if (skq == 0) vf[sr] = valid ? 1 : 0;
+    if (tid < LQ + LK - 1) {                           // table entry of k - q = k0 - q0 - (LQ - 1) + tid
+      const int64_t gi = (int64_t)k0 - q0 - (LQ - 1) + (T - 1) + tid;
+      bs[tid] = (gi >= 0 && gi <= 2 * (int64_t)T - 2) ? relb[gi * H + h] : 0.0f;
+    }
+    if (!__syncthreads_or(valid ? 1 : 0)) continue;    // no valid key in the tile: the block skips it
+
+    f32x16 s[2];
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[st][r] = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        s[st] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[st * 32 + lr][j + 32 * lk], qf[j >> 2][j & 3], s[st], 0, 0, 0);
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kl = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const float sc = f_add(s[st][r], f_mul(g, bs[kl - ql + LQ - 1]));
+        s[st][r] = vf[kl] ? sc : -INFINITY;
+        mt = fmaxf(mt, s[st][r]);
+      }
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float mn = fmaxf(m, mt);
+    const float alpha = expf(f_sub(m, mn));            // (m = -inf ahead of the first tile: 0)
+    m = mn;
+    float rs = 0.0f;
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kl = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const float p = vf[kl] ? expf(f_sub(s[st][r], mn)) : 0.0f;
+        s[st][r] = p;
+        rs = f_add(rs, p);
+      }
+    rs = f_add(rs, __shfl_xor(rs, 32, 64));
+    l = f_add(f_mul(l, alpha), rs);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[dt][r] = f_mul(acc[dt][r], alpha);
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kl = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+          acc[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[kl][dt * 32 + lr], s[st][r], acc[dt], 0, 0, 0);
+      }
+  }
+  if (!qlive) return;
+  float* o = out + ((int64_t)b * T + q) * D + h * HD;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk] = f_div(acc[dt][r], l);
+}
+
 static inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -472,5 +613,31 @@ extern "C" int qpg_wavlm_attention_f32(qpg_ctx* ctx, void* stream, const float* 
   hipLaunchKernelGGL(wavlm_attn_kernel, dim3((unsigned)((T + QT - 1) / QT), (unsigned)H, (unsigned)B), dim3(256), 0,
                      qpg_stream(stream), qkv, gate, relb, T, H, out);
   QPG_LAUNCH_CHECK("wavlm_attn_kernel");
+  return QPG_OK;
+}
+
+extern "C" int qpg_wavlm_mask_rows_f32(qpg_ctx* ctx, void* stream, float* x, const uint8_t* row_mask, int64_t M, int C) {
+  QPG_REQUIRE(ctx, "qpg_wavlm_mask_rows_f32: null context");
+  QPG_REQUIRE(x && row_mask, "qpg_wavlm_mask_rows_f32: null pointer argument");
+  QPG_REQUIRE(M >= 0 && C >= 1 && M <= ((int64_t)1 << 38) / C, "qpg_wavlm_mask_rows_f32: need M >= 0, C >= 1 and at most 2^38 "
+              "elements (M %lld, C %d)", (long long)M, C);
+  if (M == 0) return QPG_OK;
+  hipLaunchKernelGGL(wavlm_mask_rows_kernel, dim3(blocks256(M * C)), dim3(256), 0, qpg_stream(stream), x, row_mask, M * C, C);
+  QPG_LAUNCH_CHECK("wavlm_mask_rows_kernel");
+  return QPG_OK;
+}
+
+extern "C" int qpg_wavlm_attention_tiled_f32(qpg_ctx* ctx, void* stream, const float* qkv, const float* gate,
+                                             const float* relb, const uint8_t* key_mask, int B, int T, int H, float* out) {
+  QPG_REQUIRE(ctx, "qpg_wavlm_attention_tiled_f32: null context");
+  QPG_REQUIRE(qkv && gate && relb && out, "qpg_wavlm_attention_tiled_f32: null pointer argument");
+  QPG_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && H >= 1 && H <= 65535,
+              "qpg_wavlm_attention_tiled_f32: need 1 <= B, H <= 65535 and T >= 1 (B %d, T %d, H %d)", B, T, H);
+  WAVLM_UNSUP(T <= QPG_WAVLM_MAX_FRAMES_LONG, "qpg_wavlm_attention_tiled_f32: %d frames, the kernel takes at most %d", T,
+              QPG_WAVLM_MAX_FRAMES_LONG);
+  QPG_REQUIRE(((uintptr_t)qkv & 15) == 0, "qpg_wavlm_attention_tiled_f32: qkv must be 16-byte aligned");
+  hipLaunchKernelGGL(wavlm_attn_tiled_kernel, dim3((unsigned)((T + LQ - 1) / LQ), (unsigned)H, (unsigned)B), dim3(256), 0,
+                     qpg_stream(stream), qkv, gate, relb, key_mask, T, H, out);
+  QPG_LAUNCH_CHECK("wavlm_attn_tiled_kernel");
   return QPG_OK;
 }

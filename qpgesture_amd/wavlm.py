@@ -1,11 +1,14 @@
 """WavLM feature extraction on the GPU: what the reference's wav_to_wavlm / wav2wavlm (process/make_beat_dataset.py
-:328-385) get from `model.extract_features(wav)[0]` - inference, no masks, the last layer's output.
+:328-385) get from `model.extract_features(wav)[0]` - inference of 4 s windows by default; with long_inputs=True whole
+recordings of up to MAX_FRAMES_LONG frames (10.9 min), and at any length ragged batches (padding_mask) and the
+per-layer outputs (output_layer, ret_layer_results, ret_conv) of the reference's signature.
 
     from qpgesture_amd.wavlm import WavLM, load_wavlm
     model = load_wavlm("WavLM-Large.pt", device="cuda:0")        # {'cfg': dict, 'model': state_dict}
     feats = model.extract_features(wav)[0]                       # (B, n) f32 -> (B, T, D) f32 on the device
 
     python -m qpgesture_amd.wavlm --wav clip.wav --WavLM_model_path WavLM-Large.pt --out test_wavlm.npz
+    python -m qpgesture_amd.wavlm --wav clip.wav --WavLM_model_path WavLM-Large.pt --whole [--layer k]
 
 The forward pass is a chain of the qpg_wavlm_* kernels of include/qpg.h; there is no torch
 fallback: a configuration the kernels do not take raises NotImplementedError naming the field.  As in the reference the
@@ -17,6 +20,7 @@ import os
 import numpy as np
 
 MAX_FRAMES = 256          # QPG_WAVLM_MAX_FRAMES
+MAX_FRAMES_LONG = 32768   # QPG_WAVLM_MAX_FRAMES_LONG (qpg_wavlm_attention_tiled_f32)
 HEAD_DIM = 64             # QPG_WAVLM_HEAD_DIM
 WINDOW = 64000            # 4 s at 16 kHz
 SAMPLE_RATE = 16000
@@ -138,17 +142,21 @@ def window_bounds(n_samples, n_frames=240, fps=60):
 
 
 class WavLM:
-    """WavLM(cfg, device): the reference's WavLM(cfg).eval() for extract_features(wav) -> (features, None).
+    """WavLM(cfg, device): the reference's WavLM(cfg).eval() for extract_features in inference.
+    long_inputs=True (additive, off: more than MAX_FRAMES frames raise as before) admits up to MAX_FRAMES_LONG frames
+    through the tiled attention kernel; a call of at most MAX_FRAMES frames without padding_mask takes the same launches
+    and gives the same bits either way.
     normalize_input=True (additive, off as in the reference) normalises EACH WINDOW to zero mean and unit variance before
     the conv stack, so that a window's features do not depend on its batch; the upstream recipe's
     `layer_norm(wav, wav.shape)` takes one mean over the whole tensor, which is the same thing for its one-clip calls."""
 
-    def __init__(self, cfg, device="cuda:0", normalize_input=False):
+    def __init__(self, cfg, device="cuda:0", normalize_input=False, long_inputs=False):
         import torch
         check_supported(cfg)
         self.cfg = WavLMConfig(_as_dict(cfg))
         self.device = torch.device(device)
         self.normalize_input = bool(normalize_input)
+        self.long_inputs = bool(long_inputs)
         self.conv_layers = conv_layers_of(cfg)
         self.p = None
         self._relb = {}
@@ -214,6 +222,9 @@ class WavLM:
         """[2T-1][H] device table: entry k - q + T - 1 is layer 0's bias embedding of bucket(k - q); every block reads it."""
         import torch
         if T not in self._relb:
+            if T > MAX_FRAMES:                   # whole recordings come in every length: one long table is kept
+                for old in [t for t in self._relb if t > MAX_FRAMES]:
+                    del self._relb[old]
             b = relative_position_buckets(np.arange(-(T - 1), T), self.cfg.num_buckets, self.cfg.max_distance)
             self._relb[T] = torch.from_numpy(np.ascontiguousarray(self.p["rel_emb"][b])).to(self.device)
         return self._relb[T]
@@ -237,17 +248,52 @@ class WavLM:
 
     def extract_features(self, source, padding_mask=None, mask=False, ret_conv=False, output_layer=None,
                          ret_layer_results=False):
-        """(B, n) f32 samples -> ((B, T, D) f32 device tensor, None): the reference's signature and return shape."""
+        """(B, n) f32 samples -> ((B, T, D) f32 device tensor, frame mask): the reference's signature and return shape
+        (WavLM.py:323-375), its quirks included.
+          padding_mask       (B, n) bool, True = padding.  A frame is masked when all of its n // T samples are (the n % T
+                             trailing columns dropped); the conv stack still runs over the samples as given; masked frames
+                             are zeroed behind post_extract_proj and excluded as keys in every block; their own rows are
+                             computed like any other.  Returned: the (B, T) bool frame mask on the device (None without
+                             padding_mask).  A batch member without a valid frame raises ValueError (the reference
+                             returns NaN rows).
+          output_layer = k   (1-based) block k's output WITHOUT the final LayerNorm - k = encoder_layers is not None;
+                             later blocks are not launched.
+          ret_layer_results  the first result becomes (feature, layer_results): with output_layer = k the k + 1 pairs
+                             (x, None), x (T, B, D) - the encoder input behind pos_conv, then each block's output -
+                             and without output_layer an EMPTY list, as in the reference.
+          ret_conv           the feature is the encoder's input instead.  The reference hands out the tensor its encoder
+                             then works on in place, so this is x + GELU(pos_conv(x)) (masked frames zeroed first): the
+                             stage _forward names "pos_conv", not the projection's raw output."""
         if self.p is None:
             raise RuntimeError("WavLM.extract_features: load_state_dict() first")
-        for name, val in (("padding_mask", padding_mask is not None), ("mask", mask), ("ret_conv", ret_conv),
-                          ("output_layer", output_layer is not None), ("ret_layer_results", ret_layer_results)):
-            if val:
-                raise NotImplementedError("WavLM.extract_features: %s is not supported (inference of the last layer only)"
-                                          % name)
-        return self._forward(source), None
+        if mask:
+            raise NotImplementedError("WavLM.extract_features: mask is not supported (inference only)")
+        if output_layer is not None and not 1 <= int(output_layer) <= self.cfg.encoder_layers:
+            raise ValueError("WavLM.extract_features: output_layer %r is not in 1 .. %d" % (output_layer,
+                                                                                          self.cfg.encoder_layers))
+        if padding_mask is None and output_layer is None and not ret_conv and not ret_layer_results:
+            return self._forward(source), None
+        extra = {}
+        feature = self._forward(source, padding_mask=padding_mask, output_layer=output_layer, extra=extra)
+        if ret_conv:
+            feature = extra["encoder_input"]
+        if ret_layer_results:
+            feature = (feature, [(x, None) for x in extra["layer_results"]])
+        return feature, extra["frame_mask"]
 
-    def _forward(self, source, on_stage=None):
+    def frame_mask(self, padding_mask, T):
+        """(B, T) bool NumPy frame mask of a (B, n) sample mask: forward_padding_mask of the reference (WavLM.py:311-321)."""
+        import torch
+        pm = padding_mask.detach().cpu().numpy() if isinstance(padding_mask, torch.Tensor) else np.asarray(padding_mask)
+        pm = pm.astype(bool)
+        if pm.ndim != 2:
+            raise ValueError("WavLM.extract_features: padding_mask must be (B, n_samples), got %s" % (pm.shape,))
+        extra = pm.shape[1] % T
+        if extra:
+            pm = pm[:, :-extra]
+        return pm.reshape(pm.shape[0], T, -1).all(-1)
+
+    def _forward(self, source, on_stage=None, padding_mask=None, output_layer=None, extra=None):
         """The launches of one call.  on_stage(name, result), if given, is called at the stage boundaries with a view of
         the workspace: "start" (None), "features" (conv stack, [B][T][C]), "front_end" (after post_extract_proj),
         "pos_conv" (x + GELU(pos_conv(x))), "block0" (the first block's output), "blocks" (the returned result) - and
@@ -255,7 +301,12 @@ class WavLM:
         "front_norm" (the layer_norm ahead of post_extract_proj), "pos_pad" ([B][G][T + taps - 1][D / G]) and, per
         block, "block<i>.ln1", ".gate", ".qkv", ".att", ".out_proj", ".ln2", ".fc1", ".fc2".  A view is valid until the
         next launch (LayerNorms and residual GEMMs run in place).  The tests copy the views, tools/bench_wavlm.py
-        records a device event per stage."""
+        records a device event per stage.
+        padding_mask: see extract_features; one more stage, "front_mask" (front_end with the masked frames zeroed), and
+        every block's attention excludes the masked frames as keys.  output_layer = k: blocks k, k + 1, .. (0-based) are
+        not launched and "blocks" is block k - 1's output, copied.  extra, a dict, receives frame_mask (device bool or
+        None), encoder_input (a copy of "pos_conv") and layer_results (copies, (T, B, D); empty without output_layer).
+        More than MAX_FRAMES frames or a padding_mask route the attention to qpg_wavlm_attention_tiled_f32."""
         import torch
         from . import _lib
         wav = torch.as_tensor(source, dtype=torch.float32).to(self.device)
@@ -270,9 +321,26 @@ class WavLM:
         T = fr[-1]
         if T < 1:
             raise ValueError("WavLM.extract_features: %d samples are fewer than one frame's receptive field" % n)
-        if T > MAX_FRAMES:
+        if T > MAX_FRAMES and not self.long_inputs:
             raise NotImplementedError("WavLM.extract_features: %d samples give %d frames, the attention kernel takes at most "
                                       "%d (cut the input into 4 s windows)" % (n, T, MAX_FRAMES))
+        if T > MAX_FRAMES_LONG:
+            raise NotImplementedError("WavLM.extract_features: %d samples give %d frames, the tiled attention kernel takes "
+                                      "at most %d" % (n, T, MAX_FRAMES_LONG))
+        fm = key_mask = None
+        if padding_mask is not None:
+            if self.normalize_input:
+                raise NotImplementedError("WavLM.extract_features: padding_mask with normalize_input=True is not supported "
+                                          "(the window statistics would include the padding)")
+            fm_host = self.frame_mask(padding_mask, T)
+            if fm_host.shape[0] != B:
+                raise ValueError("WavLM.extract_features: padding_mask has %d rows, source %d" % (fm_host.shape[0], B))
+            empty = np.flatnonzero(fm_host.all(-1))
+            if len(empty):
+                raise ValueError("WavLM.extract_features: batch member %d has no valid frame under padding_mask" % empty[0])
+            fm = torch.from_numpy(fm_host).to(self.device)
+            key_mask = fm.to(torch.uint8).contiguous()
+        tiled = T > MAX_FRAMES or key_mask is not None
         C, D, F, H = self.conv_layers[0][0], c.encoder_embed_dim, c.encoder_ffn_embed_dim, c.encoder_attention_heads
         ws, p = self._workspace(B, n), self.p
         call = _lib.call
@@ -319,6 +387,9 @@ class WavLM:
         else:
             ln(cur, p["ln_g"], p["ln_b"], M, C, 0, x)
         mark("front_end", x, D)
+        if fm is not None:                       # x[padding_mask] = 0 ahead of pos_conv and of the residual add
+            call("qpg_wavlm_mask_rows_f32", dev, x, key_mask, M, D)
+            mark("front_mask", x, D)
         # x + GELU(pos_conv(x))
         K, G = c.conv_pos, c.conv_pos_groups
         Cg, rows = D // G, T + c.conv_pos - 1
@@ -330,7 +401,15 @@ class WavLM:
         x = y
         relb = self.position_bias_table(T)
         mark("pos_conv", x, D)
-        for i, L in enumerate(p["layers"]):
+
+        def tap(flat):                           # (T, B, D), a copy: the blocks run in place
+            return flat[:M * D].view(B, T, D).transpose(0, 1).clone(memory_format=torch.contiguous_format)
+        if extra is not None:
+            extra["frame_mask"] = fm
+            extra["encoder_input"] = x[:M * D].view(B, T, D).clone()
+            extra["layer_results"] = [] if output_layer is None else [tap(x)]
+        n_blocks = len(p["layers"]) if output_layer is None else int(output_layer)
+        for i, L in enumerate(p["layers"][:n_blocks]):
             blk = "block%d." % i
             ln(x, L["ln1_g"], L["ln1_b"], M, D, 0, h)
             mark(blk + "ln1", h, D)
@@ -338,7 +417,10 @@ class WavLM:
             mark(blk + "gate", ws["gate"], H)
             gemm(h, D, L["qkv_w"], L["qkv_b"], None, ws["qkv"], 3 * D, M, 3 * D, D)
             mark(blk + "qkv", ws["qkv"], 3 * D)
-            call("qpg_wavlm_attention_f32", dev, ws["qkv"], ws["gate"], relb, B, T, H, ws["att"])
+            if tiled:
+                call("qpg_wavlm_attention_tiled_f32", dev, ws["qkv"], ws["gate"], relb, key_mask, B, T, H, ws["att"])
+            else:
+                call("qpg_wavlm_attention_f32", dev, ws["qkv"], ws["gate"], relb, B, T, H, ws["att"])
             mark(blk + "att", ws["att"], D)
             gemm(ws["att"], D, L["out_w"], L["out_b"], x, x, D, M, D, D)
             mark(blk + "out_proj", x, D)
@@ -350,17 +432,34 @@ class WavLM:
             mark(blk + "fc2", x, D)
             if i == 0:
                 mark("block0", x, D)
+            if extra is not None and output_layer is not None:
+                extra["layer_results"].append(tap(x))
+        if output_layer is not None:             # block k's output as it stands: no final LayerNorm
+            out = x[:M * D].view(B, T, D).clone()
+            mark("blocks", out, D)
+            return out
         out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         ln(x, p["fin_g"], p["fin_b"], M, D, 0, out)
         mark("blocks", out, D)
         return out
 
 
-def load_wavlm(path, device="cuda:0", normalize_input=False):
+def load_wavlm(path, device="cuda:0", normalize_input=False, long_inputs=False):
     """The reference's wavlm_init: a checkpoint {'cfg': dict, 'model': state_dict} -> a loaded WavLM."""
     import torch
     ck = torch.load(path, map_location="cpu")
-    return WavLM(ck["cfg"], device=device, normalize_input=normalize_input).load_state_dict(ck["model"])
+    return WavLM(ck["cfg"], device=device, normalize_input=normalize_input,
+                 long_inputs=long_inputs).load_state_dict(ck["model"])
+
+
+def wav2wavlm(wav, model, device=None):
+    """wav2wavlm of the reference (make_beat_dataset.py:328-334): a whole 1-D clip -> (1, T, D) f32 NumPy through a
+    long_inputs model (`device` is accepted for the reference's signature; the model's own device is used)."""
+    wav = np.ascontiguousarray(wav, np.float32)
+    if wav.ndim != 1:
+        raise ValueError("wav2wavlm: a 1-D clip is required, got %s" % (wav.shape,))
+    print(wav.shape)
+    return model.extract_features(wav[None])[0].detach().cpu().numpy()
 
 
 def wav_to_wavlm(save_dir, prefix, wavlm_model_path, gpu="0", batch=32, n_frames=240,
@@ -414,7 +513,19 @@ def main(argv=None):
     ap.add_argument("--out", default="test_wavlm.npz")
     ap.add_argument("--gpu", type=str, default="0")
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--whole", action="store_true", help="the whole clip in one call, (1, T, D), instead of 4 s windows")
+    ap.add_argument("--layer", type=int, default=None, help="with --whole: block k's output (1-based) instead of the last")
     args = ap.parse_args(argv)
+    if args.whole:
+        model = load_wavlm(args.WavLM_model_path, device="cuda:%s" % args.gpu, long_inputs=True)
+        wav = read_wav_16k(args.wav)
+        feats = (wav2wavlm(wav, model) if args.layer is None else
+                 model.extract_features(wav[None], output_layer=args.layer)[0].cpu().numpy())
+        np.savez_compressed(args.out, wavlm=feats)
+        print(args.out, feats.shape)
+        return args.out
+    if args.layer is not None:
+        ap.error("--layer needs --whole")
     windows = cut_windows(read_wav_16k(args.wav))
     model = load_wavlm(args.WavLM_model_path, device="cuda:%s" % args.gpu)
     out = [model.extract_features(windows[i:i + args.batch])[0].cpu().numpy() for i in range(0, len(windows), args.batch)]
