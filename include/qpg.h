@@ -238,7 +238,7 @@ int qpg_text_cosine_f32(qpg_ctx*, void* stream, const float* xt, int64_t C, int 
  * 100 000 candidates): the Q x C distance matrix never reaches HBM.  Distances are bit-identical to
  * qpg_text_cosine_f32's; winner per (query, code) = minimum distance, lowest candidate index among equals.
  * cand_code: [dev] i16 [C] code of candidate c (outside [0,K): skipped, e.g. masked rows); tiles_per_chunk: 64-candidate
- * tiles per block (work granularity); `ws`: scratch of `qpg_text_percode_ws_bytes` bytes (one packed [Q][K] table);
+ * tiles per block (work granularity); `ws`: scratch of `qpg_text_percode_ws_bytes` bytes (one packed [Q][K] table; contents on entry are ignored);
  * out_dist [dev] f32 [Q][K] (`absent` where a code has no candidate), out_idx [dev] i32 [Q][K] = c + idx_base or -1,
  * out_rank optional [dev] i16 [Q][K] stable ranks; out_nn optional [dev] i32 [Q] the query's global nearest
  * neighbour over all codes (candidate index, -1 if there is no valid candidate).  K <= 1024. */
@@ -374,8 +374,8 @@ int qpg_percode_select_guarded_f64(qpg_ctx*, void* stream, const double* D, int6
  * qpg_audio_cosine_f64_h / qpg_audio_cosine_mx_h); the re-evaluation then runs on the widened, i.e. rounded, values. */
 
 /* UNCAPPED form of the guarded select (round 3): same arguments, results and arithmetic, but every list lives in `ws`
- * ([dev] qpg_percode_select_exact_ws_bytes(Q, C, K) bytes, 16-byte aligned; sized for ALL C candidates of a row inside
- * one band), so no population of near-ties can overflow it and stats[1] is never raised: the reference's scan
+ * ([dev] qpg_percode_select_exact_ws_bytes(Q, C, K) bytes, 16-byte aligned, contents on entry are ignored; sized for ALL C
+ * candidates of a row inside one band), so no population of near-ties can overflow it and stats[1] is never raised: the reference's scan
  * (GestureKNN.py:685-689) visits every candidate with a strict `<` and has no cap either.  This is the path the host
  * re-matches a clip on when a capped select or the mixed-precision sweep raised stats[1].  Five launches; K <= 1024. */
 int64_t qpg_percode_select_exact_ws_bytes(int Q, int64_t C, int K);
@@ -435,7 +435,7 @@ int qpg_percode_select_mixed_f64_cut(qpg_ctx*, void* stream, const void* D, int 
  *       shard holding the candidate.  req: [dev] W blocks of req_stride bytes, block w = [i64 count][R x u64
  *       (q_local << 48 | code << 32 | global candidate)]: the send buffer of an all-to-all.  ws: [dev] scratch of
  *       qpg_merge_mixed_ws_bytes(Q, K, fl_cap) bytes, kept for phase 2 (fl_cap = flagged (code, shard) entries per
- *       query).  stats[1] |= 4 on request / flag-list overflow: every written request is valid and every counted flag
+ *       query); contents on entry to phase 1 are ignored, phase 2 reads only what phase 1 wrote.  stats[1] |= 4 on request / flag-list overflow: every written request is valid and every counted flag
  *       entry written, the surplus is dropped and the clip must be re-matched (R = Q*K and fl_cap = K*W cannot overflow).
  *   qpg_shard_refine_f64        (every shard)  req_recv = the W request blocks received (block o from owner o); the
  *       exact f64 distance of every requested (query o*q_stride + q_local, candidate - cand_base) goes to resp block o
@@ -516,7 +516,7 @@ int qpg_l2_table_f32(qpg_ctx*, void* stream, const float* sig, int K, int Dm, fl
  *   *_pslot [G]:       phase start frame int(k/398*240) of a grid position (GestureKNN.py:632);
  *   phase:             [dev] f32 [N][Tp][2][8] (phase shift, amplitude);
  *   seed_code/seed_phase [dev f32 8x16]: init_code_phase() draw (GestureKNN.py:462-473);
- *   gate_tables:       [dev] i32 [3][Q][K] scratch: the two phase-gate candidates for every (step, previous
+ *   gate_tables:       [dev] i32 [3][Q][K] scratch (contents on entry are ignored): the two phase-gate candidates for every (step, previous
  *                      code), and the gate outcome for every (step, previous code, previous vote) — both
  *                      tabulated in parallel, so that the sequential part is Q dependent 2-byte lookups;
  *   out_codes [dev] i32 [M][30]; out_phase [dev] f32 [M][steps][8][16]; out_vote [dev] i32 [M][steps];
@@ -553,7 +553,8 @@ int qpg_match_steps_batch(qpg_ctx*, void* stream, const int16_t* aud_rank, const
  *   seed_phase [dev-readable] f32 [n_takes][8][16]; gate_tables [dev] i32 [3][Q][K] as for ONE clip;
  *   out_codes i32 [n_takes][M][30]; out_phase f32 [n_takes][M][steps][8][16]; out_vote i32 [n_takes][M][steps];
  *   take t's status pair at out_status + t x status_stride (>= 2), written last behind a system-scope fence;
- *   workspace [dev]: qpg_match_steps_takes_ws_bytes(n_takes, M, steps) bytes (the takes' trails of states).
+ *   workspace [dev]: qpg_match_steps_takes_ws_bytes(n_takes, M, steps) bytes (the takes' trails of states; contents on
+ *   entry are ignored).
  * mode: the three modality modes and QPG_MODE_PREFUSED as for qpg_match_steps.  Where the tabulated walk does not apply
  * (QPG_MODE_SERIAL_WALK, a geometry the tabulation refuses) the call returns QPG_EUNSUP before launching anything: the
  * caller walks the takes one at a time. */
@@ -605,7 +606,7 @@ int qpg_fuse_best_ranked(qpg_ctx*, void* stream, const int16_t* rank, const int3
  *   workspace [dev], qpg_match_steps_nophase_ws_bytes(n_chains, M, steps, K) bytes: next u16 [Q][2][K] (Q = n_chains M
  *   steps; [q][s][p]: the previous code after step q when side s, 0 audio / 1 text, is taken from previous code p; 0xFFFF:
  *   none) followed by pick i32 [Q][2][K] (that side's candidate of c*, -1: none); a side the mode does not use holds
- *   0xFFFF / -1.  M == 0 writes the status pairs only.
+ *   0xFFFF / -1.  Contents on entry are ignored.  M == 0 writes the status pairs only.
  * Two launches: the tables for every (step, previous code), then one block per chain that follows next through LDS. */
 #define QPG_NOPHASE_KMAX 16
 size_t qpg_match_steps_nophase_ws_bytes(int n_chains, int M, int steps, int K);
@@ -660,7 +661,8 @@ int qpg_unpack_min_u64(qpg_ctx*, void* stream, const uint64_t* packed, int64_t n
  * w: [dev] f32 [taps][Cin_pad][Cout_pad] repacked weights (Cin_pad % 16 == 0, Cout_pad % 128 == 0, zero padded);
  * bias: [dev] f32 [Cout_pad] or NULL; residual: indexed like y, or NULL; y: [dev] f32 [B][T_y][Cout].
  * ws / ws_floats: optional [dev] f32 scratch; when given and the launch would not fill the chip (short sequences),
- * the contraction is split over up to 8 block groups whose partial sums are added in a fixed order. */
+ * the contraction is split over up to 8 block groups whose partial sums are added in a fixed order (how many: by the
+ * shapes and ws_floats, never by what ws holds - contents on entry are ignored). */
 int qpg_conv1d_f32(qpg_ctx*, void* stream, const float* x, int B, int T_in, int Cin, const float* w,
                    const float* bias, int taps, int Cin_pad, int Cout, int Cout_pad, int in_stride, int in_offset,
                    int dil, int T_out, int out_stride, int out_offset, int T_y, const float* residual, int relu_in,
@@ -760,7 +762,7 @@ typedef struct {
   const float* dec_res_pack[QPG_VQ_MAX_DOWN][QPG_VQ_MAX_DEPTH];
 } qpg_vq_model;
 
-/* floats of scratch the two calls below need for a batch of B sequences of T pose frames */
+/* floats of scratch the two calls below need for a batch of B sequences of T pose frames (contents on entry are ignored) */
 int64_t qpg_vq_workspace_floats(const qpg_vq_model* m, int B, int T);
 /* x: [dev] f32 [B][T][in_dim] (T %% 2^down_t == 0) -> ids [dev] i64 [B][T/2^down_t]; latent: optional [dev] f32
  * [B][T/2^down_t][emb] (pre-quantisation encoder output); margin: optional [dev] f32 [B][T/2^down_t] runner-up minus best. */
@@ -799,7 +801,7 @@ int qpg_pose_to_euler_f64(qpg_ctx*, void* stream, const float* poses, int64_t T,
  * out [dev] f32 [n_frames][4][8] = [p, f, a, b] x 8 channels (the reference's (T,4,1,8,1) array); v_out: optional [dev]
  * f32 [n_frames][8][2] the BN'd fc output (x, y) that p is the atan2' of; latent_out: optional [dev] f32
  * [n_frames][8][240].  ws: [dev] f32 scratch of at least (n_frames + 2 QPG_PAE_HALO - 1) * QPG_PAE_WS_STRIDE floats
- * (the f32 velocities of the rows the chunk reads).  A frame's result does not depend on frame0, n_frames or the
+ * (the f32 velocities of the rows the chunk reads; contents on entry are ignored).  A frame's result does not depend on frame0, n_frames or the
  * other clips (bit-identical however a batch is chunked).  n_frames = 0 is a no-op. */
 #define QPG_PAE_CHANNELS 135
 #define QPG_PAE_MID 15
@@ -837,8 +839,8 @@ int qpg_pae_phase_f32(qpg_ctx*, void* stream, const float* params, const double*
  *   poses  [dev] f32 [n_frames][135]: normalised poses (pose - mean) / clip(std, 0.01) in f64, rounded once, of one
  *     or many clips concatenated;  starts [dev] i64 [batch]: window b is poses[starts[b] .. starts[b] + 239] (the
  *     caller keeps windows inside their clip; a start outside 0 .. n_frames - 240 yields a NaN window).
- *   ws     [dev] f32 scratch of qpg_pae_train_ws_floats(batch) floats, 16-byte aligned.  The forward leaves every
- *     activation there for the backward of the same batch; nothing is allocated and nothing waits for the host. */
+ *   ws     [dev] f32 scratch of qpg_pae_train_ws_floats(batch) floats, 16-byte aligned; contents on entry to the forward
+ *     are ignored.  The forward leaves every activation there for the backward of the same batch; nothing is allocated and nothing waits for the host. */
 #define QPG_PAET_OFF_TPI 0
 #define QPG_PAET_OFF_ARGS 1
 #define QPG_PAET_OFF_FREQS 241
@@ -884,7 +886,8 @@ int qpg_pae_adamw_f32(qpg_ctx*, void* stream, float* p, const float* g, float* m
 
 /* ---- VQ-VAE training step (codebook/train.py:120-148): VQVAE.forward's loss terms, the bottleneck statistics,
  * the EMA codebook update, the loss gradient and Adam.  Reductions are ordered two-stage sums in f64
- * (deterministic).  `ws` is a caller-owned scratch of at least qpg_vq_reduce_ws_bytes() bytes. ---- */
+ * (deterministic).  `ws` is a caller-owned scratch of at least qpg_vq_reduce_ws_bytes() bytes; here and in
+ * the calls below its contents on entry are ignored. ---- */
 int64_t qpg_vq_reduce_ws_bytes(void);
 
 /* vqvae.py:244-267.  x_out, x_target: [dev] f32 [B][T][C].  commit_loss: optional [dev] f32 scalar.
@@ -945,7 +948,8 @@ int qpg_adam_step_f32(qpg_ctx*, void* stream, float* param, const float* grad, f
  *   db [Cout_pad] (optional; accumulate_bias != 0 adds to it: the two parity sets of a transposed convolution
  *   share one bias) from the layer input x (relu_in as in the forward call) and dy.  The position axis is
  *   split over thread blocks; ws holds the partial sums (qpg_conv1d_wgrad_ws_floats(taps,Cin_pad,Cout_pad,splits)
- *   floats for `splits` partials; more workspace = more parallelism, 1 partial is the minimum). */
+ *   floats for `splits` partials; more workspace = more parallelism, 1 partial is the minimum; contents on entry are
+ *   ignored, here and in qpg_conv1d_bwd_data_f32's split-K scratch). */
 int qpg_conv1d_bwd_data_f32(qpg_ctx*, void* stream, const float* dy, int B, int T_in, int C_dy, const float* w_fwd,
                             int taps, int fwd_Cin, int fwd_Cin_pad, int fwd_Cout_pad, int tap_base, int tap_step,
                             int in_stride, int in_offset, int dil, int T_out, int out_stride, int out_offset, int T_y,

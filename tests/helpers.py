@@ -81,23 +81,28 @@ def sweep_text_unfused(knn, queries):
     return dist, idx, D
 
 
-def merge_mixed_by_hand(recv, W, src_stride, dist_off, idx_off, Q, K, eps1, eps2, shards, R=4096, fl_cap=1024):
+def merge_mixed_by_hand(recv, W, src_stride, dist_off, idx_off, Q, K, eps1, eps2, shards, R=4096, fl_cap=1024, ws=None,
+                        ws_bytes=None, out=None):
     """The cross-shard merge of mixed-precision tables (qpg_merge_mixed_phase1_f64 -> qpg_shard_refine_f64 on every shard ->
     qpg_merge_mixed_phase2_f64) on ONE device, for one owner that holds all Q queries, with the two byte exchanges done by
     hand.  recv: what the all-gather leaves on every rank (W table blocks src_stride bytes apart, distances at dist_off,
     global candidate indices at idx_off).  shards: per row shard a dict with the arguments of ITS refine call - cand_base
     (global index of its first candidate), base, base_is_f16, T, F, cand_t, G, tap_stride, q32, qn2, cn2.
-    Returns (dist, idx, rank, stats as numpy, requests per shard)."""
+    ws: the caller's workspace (u8, at least qpg_merge_mixed_ws_bytes; contents on entry are ignored: it is handed to
+    phase 1 as it is and phase 2 reads what phase 1 left); ws_bytes: the size to state instead of ws.numel(); out: the
+    caller's (dist, idx, rank) tensors.  Returns (dist, idx, rank, stats as numpy, requests per shard)."""
     import torch
     from qpgesture_amd import _lib
     from qpgesture_amd.constant import ABSENT_DIST
     dev = recv.device
     req_stride, resp_stride = 8 + 8 * R, 8 + 8 * R
     req = torch.zeros((W * req_stride,), dtype=torch.uint8, device=dev)
-    ws = torch.empty((int(_lib.load().qpg_merge_mixed_ws_bytes(Q, K, fl_cap)),), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty((int(_lib.load().qpg_merge_mixed_ws_bytes(Q, K, fl_cap)),), dtype=torch.uint8, device=dev)
+    ws_bytes = ws.numel() if ws_bytes is None else ws_bytes
     stats = torch.zeros((4,), dtype=torch.int32, device=dev)
     _lib.call("qpg_merge_mixed_phase1_f64", dev, recv, W, src_stride, dist_off, idx_off, Q, K, float(ABSENT_DIST), eps1, R,
-              req, req_stride, ws, ws.numel(), stats, fl_cap, -1)
+              req, req_stride, ws, ws_bytes, stats, fl_cap, -1)
     counts = [int(req[w * req_stride:w * req_stride + 4].view(torch.int32)[0]) for w in range(W)]   # header: count | flags
     resp_recv = torch.zeros((W * resp_stride,), dtype=torch.uint8, device=dev)
     for w in range(W):                                       # all-to-all by hand: owner 0's block w -> shard w's block 0
@@ -111,10 +116,10 @@ def merge_mixed_by_hand(recv, W, src_stride, dist_off, idx_off, Q, K, eps1, eps2
                   int(s["base_is_f16"]), s["T"], s["F"], s["cand_t"], s["G"], 6, s["tap_stride"], s["q32"], s["qn2"], s["cn2"],
                   resp, resp_stride, 0, None, R // Q)
         resp_recv[w * resp_stride:(w + 1) * resp_stride] = resp[:resp_stride]
-    d = torch.empty((Q, K), dtype=torch.float64, device=dev)
-    ix = torch.empty((Q, K), dtype=torch.int32, device=dev)
-    rk = torch.empty((Q, K), dtype=torch.int16, device=dev)
-    _lib.call("qpg_merge_mixed_phase2_f64", dev, recv, W, src_stride, idx_off, Q, K, float(ABSENT_DIST), ws, ws.numel(),
+    d, ix, rk = out if out is not None else (torch.empty((Q, K), dtype=torch.float64, device=dev),
+                                             torch.empty((Q, K), dtype=torch.int32, device=dev),
+                                             torch.empty((Q, K), dtype=torch.int16, device=dev))
+    _lib.call("qpg_merge_mixed_phase2_f64", dev, recv, W, src_stride, idx_off, Q, K, float(ABSENT_DIST), ws, ws_bytes,
               resp_recv, resp_stride, d, ix, rk, stats, fl_cap, eps2)
     torch.cuda.synchronize()
     return d, ix, rk, stats.cpu().numpy(), counts

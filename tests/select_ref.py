@@ -257,7 +257,7 @@ class AudioCase:
     """A small database + queries with the planted edge cases, its exact distances and reference tables.  Geometry: T = 180,
     G = 26 grid positions 6 frames apart, 6 taps of stride 2 (the product's), F features (32 unless stated)."""
 
-    def __init__(self, name, N, Q, K, E, seed=0, F=32, half=False, crowded=None, eps1=None, shards=()):
+    def __init__(self, name, N, Q, K, E, seed=0, F=32, half=False, crowded=None, eps1=None, shards=(), one_code=None):
         self.name, self.N, self.Q, self.K, self.E, self.F, self.half = name, N, Q, K, float(E), F, half
         self.eps1 = BAND_RATIO * self.E if eps1 is None else float(eps1)
         self.eps2 = 1e-12
@@ -294,9 +294,20 @@ class AudioCase:
             base = self.base16.astype(np.float32)                          # everything is defined on the rounded track
         code = code.reshape(-1)
         code[rng.random(C) < 0.03] = -1                                    # masked candidates
+        if one_code is not None:
+            # the tier-1 list's overflow: every frame is one vector u plus noise of relative size `a`, so every candidate row
+            # is [u] * 6 + noise, and ALL of them carry one code.  Query 0 is [u] * 6 itself: its distances are second order
+            # in the noise (~a^2 / 2, spread ~a^2 / 10) - all inside one band.  Every other query is an ordinary random row:
+            # its distances vary in first order (~a / sqrt(6 F)) and only a few candidates are near the minimum.
+            code_k, a = one_code
+            u = rng.standard_normal(F, dtype=np.float32)
+            base = (u[None, None, :] * (1.0 + a * rng.standard_normal((N, T, F), dtype=np.float32))).astype(np.float32)
+            code = np.full(C, code_k, np.int16)
         self.base, self.cand_code = base, code
         self.cand_t = (np.arange(G) * 6).astype(np.int32)
         self.q32 = rng.standard_normal((Q, N_TAPS * F), dtype=np.float32)
+        if one_code is not None:
+            self.q32[0] = np.tile(u, N_TAPS)
         self.C = C
 
     @functools.cached_property
@@ -330,6 +341,23 @@ class AudioCase:
 
 # name -> constructor arguments.  E per case is the value at which `admissible` holds (tests/test_select_contract_cpu.py
 # checks it and prints the band populations); the (N, Q, K) list, the f16 track and the product band are the issue's.
+# overflow: N = 80 windows x G = 26 = 2080 candidates under ONE code, all within the band of query 0 - more than the
+# MIX_LIST = 2048 entries of a tier-1 list, so the mixed select must raise stats[1] & 1; query 1 has an ordinary row.  Not in
+# AUDIO_CASES: its verdict is NOT determined by the input (condition (b) fails by construction), and what it is for is the
+# state the overflow path leaves in the workspace (tests/test_gpu_scratch_contract.py).
+# (E = 1e-5 with a band of 4e-4: query 0's spread, ~2.7e-4, fits inside eps1 - 2 E; query 1's, ~1e-2, is 25 bands wide.)
+OVERFLOW_CASE = dict(N=80, Q=2, K=96, E=1e-5, eps1=4e-4, seed=9, one_code=(3, 0.02))
+
+
+def band_counts(c, eps):
+    """Per query of case c: candidates (valid code) within eps of their code's exact minimum."""
+    code = c.cand_code.astype(np.int64)
+    valid = (code >= 0) & (code < c.K)
+    ed = c.ref[0]
+    cmin = np.where(valid[None], ed[:, np.where(valid, code, 0)], -np.inf)
+    return (valid[None] & (c.exact <= cmin + eps)).sum(axis=1)
+
+
 AUDIO_CASES = {
     "base": dict(N=48, Q=48, K=96, E=1e-3, seed=1, shards=(2, 3)),
     "odd": dict(N=37, Q=5, K=7, E=3e-3, seed=2),
@@ -346,6 +374,8 @@ PRODUCT_CASE = dict(N=48, Q=12, K=96, seed=28, crowded=-7.2)
 
 @functools.lru_cache(maxsize=None)
 def audio_case(name):
+    if name == "overflow":
+        return AudioCase(name, **OVERFLOW_CASE)
     return AudioCase(name, **AUDIO_CASES[name])
 
 

@@ -48,11 +48,13 @@ def _device(name):
     return _Device(W.case(name))
 
 
-def _call(D, mode, k, seeds, coins=None, guard=None, tables=False, drop=(), M=None, steps=None, stride=2, made=None):
+def _call(D, mode, k, seeds, coins=None, guard=None, tables=False, drop=(), M=None, steps=None, stride=2, made=None, ws=None,
+          ws_state=None, outs=None):
     """One qpg_match_steps_nophase call over len(seeds) chains -> the outputs as NumPy arrays (everything is pre-filled
     with -9 / 0xEEEE: a word the call did not write shows).  coins: [n_chains][M steps] or None.  drop: argument names
     passed as NULL.  tables: also the workspace's next / pick.  made: a list that receives the workspace and the output
-    tensors before the call (for a call that raises)."""
+    tensors before the call (for a call that raises).  ws: the caller's workspace (an i16 tensor of at least the stated
+    size) instead of the 0xEEEE one; ws_state: the size to state; outs: the caller's output tensors (codes, side, cand, status) instead of the -9 ones."""
     import torch
     from qpgesture_amd import _lib
     P = D.P
@@ -62,10 +64,13 @@ def _call(D, mode, k, seeds, coins=None, guard=None, tables=False, drop=(), M=No
     cpw = min(4 * steps, 30)
     rows = slice(0, max(Q, 1))
     ws_bytes = int(_lib.load().qpg_match_steps_nophase_ws_bytes(n, max(M, 1), steps, P.K))
-    ws = torch.full((ws_bytes // 2,), -4370, dtype=torch.int16, device=DEV)                   # 0xEEEE
-    o = {k_: torch.full(shape, -9, dtype=torch.int32, device=DEV)
-         for k_, shape in dict(codes=(n, max(M, 1), cpw), side=(n, max(M, 1) * steps), cand=(n, max(M, 1) * steps),
-                               status=(n, stride)).items()}
+    if ws is None:
+        ws = torch.full((ws_bytes // 2,), -4370, dtype=torch.int16, device=DEV)               # 0xEEEE
+    ws_bytes = ws_bytes if ws_state is None else ws_state
+    o = outs if outs is not None else {
+        k_: torch.full(shape, -9, dtype=torch.int32, device=DEV)
+        for k_, shape in dict(codes=(n, max(M, 1), cpw), side=(n, max(M, 1) * steps), cand=(n, max(M, 1) * steps),
+                              status=(n, stride)).items()}
     if made is not None:
         made.extend([ws] + list(o.values()))
     a = dict(aud_rank=D.aud_rank[rows], aud_idx=D.aud_idx[rows], txt_rank=D.txt_rank[rows], txt_idx=D.txt_idx[rows],

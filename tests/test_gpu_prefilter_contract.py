@@ -61,8 +61,10 @@ class _Images:
         self.R, self.D, self.Q = xs.shape[0], xs.shape[1], qn.shape[0]
         self.xs_t = torch.from_numpy(xs).to(self.dev)
         self.qn_t = torch.from_numpy(qn).to(self.dev)
-        self.rows = torch.zeros((int(lib.qpg_hl_rows_bytes(self.R, self.D)),), dtype=torch.uint8, device=self.dev)
-        self.cols = torch.zeros((int(lib.qpg_hl_cols_bytes(self.Q, self.D)),), dtype=torch.uint8, device=self.dev)
+        # the pack kernels write every fragment the GEMMs read (the last column chunk's padding queries as zeros): what the
+        # images held before is ignored, so they start from a plausible non-zero pattern, not from zeros
+        self.rows = torch.full((int(lib.qpg_hl_rows_bytes(self.R, self.D)),), 0x3C, dtype=torch.uint8, device=self.dev)
+        self.cols = torch.full((int(lib.qpg_hl_cols_bytes(self.Q, self.D)),), 0x3C, dtype=torch.uint8, device=self.dev)
         _lib.call("qpg_hl_pack_rows", self.dev, self.xs_t, self.R, self.D, self.rows, self.rows.numel())
         _lib.call("qpg_hl_pack_cols", self.dev, self.qn_t, self.Q, self.D, self.cols, self.cols.numel())
 

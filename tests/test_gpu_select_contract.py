@@ -56,8 +56,9 @@ def _workspace(K):
     return torch.zeros((int(_lib.load().qpg_percode_select_mixed_ws_bytes(Qmax, K)),), dtype=torch.uint8, device="cuda:0")
 
 
-def _mixed(name, D_in, eps1, eps2, use_ws, lo=0, hi=None, ld_pad=0, idx_base=0, out=None, cut=None, ranks=True):
+def _mixed(name, D_in, eps1, eps2, use_ws, lo=0, hi=None, ld_pad=0, idx_base=0, out=None, cut=None, ranks=True, ws=None, rank_out=None):
     """One call of the mixed select (or its cut form) on D_in [Q][C] (f32 or f64; NaN in the ld_pad padding columns).
+    ws: the caller's own workspace (u8, zero-filled once) instead of the shared one of _workspace(K).
     -> dist, idx, rank (numpy), stats [4], tier-1 list length per query (workspace form; else None)."""
     import torch
     from qpgesture_amd import _lib
@@ -71,9 +72,9 @@ def _mixed(name, D_in, eps1, eps2, use_ws, lo=0, hi=None, ld_pad=0, idx_base=0, 
         idx = torch.full((Q, K), -7, dtype=torch.int32, device=dev)
     else:
         dist, idx = out
-    rank = torch.full((Q, K), -7, dtype=torch.int16, device=dev) if ranks else None
+    rank = (torch.full((Q, K), -7, dtype=torch.int16, device=dev) if rank_out is None else rank_out) if ranks else None
     stats = torch.zeros((4,), dtype=torch.int32, device=dev)
-    ws = _workspace(K) if use_ws else None
+    ws = (_workspace(K) if ws is None else ws) if use_ws else None
     args = [D, int(D_in.dtype == np.float32), D.stride(0), Q, o["code"], C, K, R.ABSENT, idx_base, dist, idx, rank, 0, 0,
             o["base"], T, c.F, o["cand_t"], G, R.N_TAPS, R.TAP_STRIDE, o["q32"][:Q], o["qn2"][:Q], o["cn2"], float(eps1),
             float(eps2), stats, ws, ws.numel() if use_ws else 0, o["half"]]
@@ -287,7 +288,7 @@ def test_cross_shard_merge_returns_the_exact_tables(W, noise):
     assert np.abs(d.cpu().numpy() - rd)[ri >= 0].max() <= c.E
 
 
-def _f64_select(name, which, D, q_block=0, block_stride=0, out=None, ranks=True):
+def _f64_select(name, which, D, q_block=0, block_stride=0, out=None, ranks=True, ws=None, ws_bytes=None, rank_out=None):
     """qpg_percode_select_guarded_f64 / _exact_f64 on the f64 matrix D (device) with eps = 1e-12.  Plain tables are prefilled
     with sentinels; `out` = (dist, idx) views of an exchange buffer.  -> dist, idx, rank (device tensors), stats (numpy)."""
     import torch
@@ -296,13 +297,14 @@ def _f64_select(name, which, D, q_block=0, block_stride=0, out=None, ranks=True)
     dev, Q, K, C = o["dev"], c.Q, c.K, o["C"]
     if out is None:
         out = (torch.full((Q, K), float("nan"), dtype=torch.float64, device=dev), torch.full((Q, K), -7, dtype=torch.int32, device=dev))
-    rank = torch.full((Q, K), -7, dtype=torch.int16, device=dev) if ranks else None
+    rank = (torch.full((Q, K), -7, dtype=torch.int16, device=dev) if rank_out is None else rank_out) if ranks else None
     stats = torch.zeros((4,), dtype=torch.int32, device=dev)
     args = [D, D.stride(0), Q, o["code"], C, K, R.ABSENT, 0, out[0], out[1], rank, q_block, block_stride, o["base"], T, c.F,
             o["cand_t"], G, R.N_TAPS, R.TAP_STRIDE, o["q32"], 1e-12, stats, o["half"]]
     if which == "exact":
-        ws = torch.empty((int(_lib.load().qpg_percode_select_exact_ws_bytes(Q, C, K)),), dtype=torch.uint8, device=dev)
-        args += [ws, ws.numel()]
+        if ws is None:
+            ws = torch.empty((int(_lib.load().qpg_percode_select_exact_ws_bytes(Q, C, K)),), dtype=torch.uint8, device=dev)
+        args += [ws, ws.numel() if ws_bytes is None else ws_bytes]
     _lib.call("qpg_percode_select_%s_f64" % which, dev, *args)
     torch.cuda.synchronize()
     return out[0], out[1], rank, stats.cpu().numpy()

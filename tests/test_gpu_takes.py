@@ -123,7 +123,7 @@ def test_the_library_refuses_the_serial_walk_with_eunsup(fullsize):
     T = knn.sweep_tables(te_i, te_c, M)
     dev, S, Q = db.device, 4, M * 8
     z = lambda *shape, dt=torch.int32: torch.zeros(shape, dtype=dt, device=dev)          # noqa: E731
-    ws = torch.zeros((int(_lib.load().qpg_match_steps_takes_ws_bytes(S, M, 8)),), dtype=torch.uint8, device=dev)
+    ws = torch.full((int(_lib.load().qpg_match_steps_takes_ws_bytes(S, M, 8)),), 0x3C, dtype=torch.uint8, device=dev)    # (contents on entry are ignored)
     with pytest.raises(_lib.Unsupported, match="tabulated walk"):
         _lib.call("qpg_match_steps_takes", dev, T["aud_rank"], T["aud_idx"], T["txt_rank"], T["txt_idx"], db.pos_rank,
                   db.freq_rank, db.code, db.code.shape[1], db.aud_cidx, db.aud_pslot, db.Ga, db.txt_cidx, db.txt_pslot,

@@ -322,14 +322,19 @@ def test_walk_batch(n_chains, stride):
         _lib.set_option(DEV, _lib.QPG_OPT_GATE_DEDUP_FROM_CHAINS, 1)
 
 
-def _takes(D, mode, n_takes, stride=2):
+def _takes(D, mode, n_takes, stride=2, fill=0x3C, ws=None, ws_bytes=None, o=None, status=None):
+    """One qpg_match_steps_takes call.  The workspace's contents on entry are ignored by the library: it is byte-filled with
+    `fill` (not zeros), or the caller hands its own `ws` (u8) and the size to state."""
     import torch
     from qpgesture_amd import _lib
     P = D.P
-    o = _outputs(P, n_takes, P.M)
-    status = torch.full((n_takes * stride,), -9, dtype=torch.int32, device=DEV)
+    o = _outputs(P, n_takes, P.M) if o is None else o
+    if status is None:
+        status = torch.full((n_takes * stride,), -9, dtype=torch.int32, device=DEV)
     nb = int(_lib.load().qpg_match_steps_takes_ws_bytes(n_takes, P.M, P.steps))
-    ws = torch.zeros((max(nb, 16),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.full((max(nb, 16),), fill, dtype=torch.uint8, device=DEV)
+    nb = nb if ws_bytes is None else ws_bytes
     _lib.call("qpg_match_steps_takes", DEV, *D.head(slice(0, P.Q), mode, P.M), n_takes, _t(P.seed_codes[:n_takes], np.int32),
               _t(P.seed_phases[:n_takes], np.float32), o["gate"], o["codes"], o["phase"], o["vote"], status, stride, None,
               ws, nb)

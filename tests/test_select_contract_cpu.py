@@ -143,3 +143,18 @@ def test_the_text_case_has_its_planted_rows():
     dist, idx, rank, nn = t.ref
     assert (idx[:, 3] == -1).all() and nn[7] == 699            # the absent code; the query that is a (duplicated) row
     assert len(src) % 64 == 0 and (seg[::16] == seg[15::16]).all()          # a tile lies inside one code
+
+
+def test_the_overflow_case_overflows_query_0_and_leaves_query_1_ordinary():
+    """tests/test_gpu_scratch_contract.py's `overflow` case: 2080 candidates under one code.  Whatever matrix within E of the
+    exact distances the select is handed, a candidate within eps1 - 2 E of its code's exact minimum is within eps1 of the
+    approximate one: query 0 has more of those than a tier-1 list holds, so the list MUST overflow.  A candidate outside
+    eps1 + 2 E cannot be listed: query 1 stays below half the capacity."""
+    c = R.audio_case("overflow")
+    assert c.C == 80 * 26 == 2080 > R.MIX_LIST and (c.cand_code == 3).all() and c.Q == 2
+    surely, possibly = R.band_counts(c, c.eps1 - 2 * c.E), R.band_counts(c, c.eps1 + 2 * c.E)
+    print("overflow case: query 0 lists %d .. %d of %d candidates, query 1 %d .. %d (capacity %d)"
+          % (surely[0], possibly[0], c.C, surely[1], possibly[1], R.MIX_LIST))
+    assert surely[0] > R.MIX_LIST
+    assert possibly[1] < R.MIX_LIST // 2
+    assert surely[1] >= 1 and np.ptp(c.exact[1]) > 10 * c.eps1           # an ordinary row: a spread far wider than the band
