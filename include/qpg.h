@@ -1027,6 +1027,38 @@ int qpg_wavlm_mask_rows_f32(qpg_ctx*, void* stream, float* x, const uint8_t* row
 int qpg_wavlm_attention_tiled_f32(qpg_ctx*, void* stream, const float* qkv, const float* gate, const float* relb,
                                   const uint8_t* key_mask, int B, int T, int H, float* out);
 
+/* ---- Sentence embeddings (a BERT-shaped post-LN encoder as sentence-transformers wraps it, inference): the three kernels
+ * qpgesture_amd/sentence.py chains with qpg_wavlm_gemm_f32 and qpg_wavlm_layernorm_f32.  Activations are PACKED RAGGED
+ * ROWS: sentence s < S owns the token rows seq_start[s] .. seq_start[s + 1] of an [R][D] f32 array, seq_start [dev] i32
+ * [S + 1] with seq_start[0] = 0 and seq_start[S] = R; nothing is padded, nothing is masked.  max_len is the caller's
+ * statement of the longest sentence; it sizes the launch and is what the host-side checks see.  What the device arrays
+ * hold is never trusted for an address: sentence bounds that are not 0 <= start < end <= R with end - start <= max_len,
+ * an id outside [0, vocab) and a position >= max_pos OR a bit into *err ([dev] i32, zeroed by the caller, read when it
+ * synchronises) and the rows concerned are not written.  A sentence's result does not depend on which other sentences
+ * share the launch. ---- */
+#define QPG_BERT_HEAD_DIM 32
+#define QPG_BERT_MAX_TOKENS 128
+#define QPG_BERT_ERR_SEQ 1 /* *err bit: seq_start does not describe rows inside [0, R) of at most max_len each */
+#define QPG_BERT_ERR_ID 2  /* *err bit: an id outside [0, vocab)                                                */
+#define QPG_BERT_ERR_POS 4 /* *err bit: a token position >= max_pos                                             */
+
+/* x[r] = LayerNorm((word[ids[r]] + type0) + pos[r - seq_start[s(r)]]) gamma + beta (biased variance of the centred values,
+ * eps inside the root): ids [dev] i32 [R], word [vocab][D], pos [max_pos][D], type0 [D] (token type 0's row), x [R][D].
+ * max_len > max_pos: QPG_EINVAL, nothing launched. */
+int qpg_bert_embed_ln_f32(qpg_ctx*, void* stream, const int32_t* ids, const int32_t* seq_start, int S, int64_t R,
+                          int max_len, const float* word, int vocab, const float* pos, int max_pos, const float* type0,
+                          const float* gamma, const float* beta, int D, float eps, float* x, int32_t* err);
+
+/* Self-attention of one block: qkv [R][3 H 32] (q | k | v, q already scaled by 32^-0.5), out [R][H 32] = softmax_k(q k^T) v
+ * per (sentence, head) over the sentence's own rows, the running maximum subtracted before exp, the sum over the keys taken
+ * in key order for every query.  max_len > QPG_BERT_MAX_TOKENS: QPG_EUNSUP, nothing launched.  qkv, out 16-byte aligned. */
+int qpg_bert_attention_f32(qpg_ctx*, void* stream, const float* qkv, const int32_t* seq_start, int S, int64_t R, int max_len,
+                           int H, float* out, int32_t* err);
+
+/* out[s] = (sum of x[r] over the rows of sentence s, in token order) / (their number): x [R][D], out [S][D]. */
+int qpg_bert_mean_pool_f32(qpg_ctx*, void* stream, const float* x, const int32_t* seq_start, int S, int64_t R, int max_len,
+                           int D, float* out, int32_t* err);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

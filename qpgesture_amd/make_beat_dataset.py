@@ -11,7 +11,9 @@ writes <save_dir>/<prefix>/<prefix>_<split>_240_code.npz['code'] int64 (N,30) โ
 as --train_codebook.  With --WavLM_model_path ({'cfg', 'model'} checkpoint) it also reads the same files' ['wav']
 (N,64000) and writes <prefix>_<split>_240_WavLM.npz['wavlm'] f32 (N,199,D), the --train_wavlm files, through the HIP
 WavLM of qpgesture_amd/wavlm.py; without the flag nothing else changes.  Same flags as codebook/configs/parse_args.py.
-Steps 1, 2 and 4 (BVH cutting, vq-wav2vec and sentence embeddings) are out of scope (SURVEY.md ยง2 row 22).
+The sentence embeddings of step 4 (make_txt_dataset's `context` column) are qpgesture_amd/sentence.py (txt_to_context,
+`python -m qpgesture_amd.sentence`); steps 1 and 2 (BVH cutting) and step 4's vq-wav2vec are out of scope (SURVEY.md ยง2
+row 22).
 
 The reference encodes one window per call in a Python loop (:314-316); windows are independent, so they are
 encoded in batches of 256 on the GPU (qpg_vq_encode_f32)."""
@@ -68,8 +70,8 @@ def main(argv=None):
     from .checkpoint import load_config
     args = build_parser().parse_args(argv)
     if args.step != "3":
-        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm) is implemented; steps 1/2/4 are BVH cutting, "
-                         "vq-wav2vec and sentence embeddings, out of scope")
+        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm) is implemented; steps 1/2 (BVH cutting) and step 4's "
+                         "vq-wav2vec are out of scope, step 4's sentence embeddings are `python -m qpgesture_amd.sentence`")
     written = dataset_to_code(args.save_dir, args.prefix, 240, args.VQVAE_model_path, load_config(args.config),
                               gpu=args.gpu, batch=args.batch)
     if args.WavLM_model_path:

@@ -411,3 +411,69 @@ def make_wav(seed, B, n):
     wav *= 0.6 + 0.4 * np.sin(2 * np.pi * (rng.uniform(1.0, 4.0, (B, 1)) * t + rng.uniform(0, 1, (B, 1))))
     wav += rng.standard_normal((B, n)) * 0.02
     return np.ascontiguousarray(wav, np.float32)
+
+
+# ----------------------------------------------------------------------------------------------
+# Sentence encoder (transformers' BertModel as sentence-transformers wraps it): seeded weights with BertModel's key
+# names, and a small word list in vocab.txt's form
+# ----------------------------------------------------------------------------------------------
+def _bert_cfg(hidden, layers, heads, ffn, vocab):
+    return dict(model_type="bert", hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads,
+                intermediate_size=ffn, vocab_size=vocab, max_position_embeddings=512, type_vocab_size=2,
+                hidden_act="gelu", layer_norm_eps=1e-12, position_embedding_type="absolute", pad_token_id=0)
+
+
+BERT_TINY = _bert_cfg(64, 2, 2, 128, 97)             # every kernel path at the smallest widths
+BERT_MINILM = _bert_cfg(384, 6, 12, 1536, 30522)     # paraphrase-MiniLM-L6-v2's config.json
+
+
+def make_bert_state_dict(seed, cfg=None):
+    """No MiniLM checkpoint ships with the reference.  Seeded weights with the key names and shapes of
+    transformers.BertModel(config, add_pooling_layer=False).state_dict() (`cfg` a config.json dict, default BERT_TINY).
+    Linear weights N(0, 1 / fan_in) with the query and key weights times 2 (gain 1 gives near-uniform softmax rows, which
+    would test nothing; 3 makes the f32 evaluation itself chaotic), embeddings N(0, 0.5^2), biases and LayerNorm gains
+    non-trivial."""
+    cfg = dict(BERT_TINY if cfg is None else cfg)
+    rng = _rng(seed)
+    D, F = cfg["hidden_size"], cfg["intermediate_size"]
+    sd = {}
+
+    def f32(a):
+        return np.ascontiguousarray(a, np.float32)
+
+    def norm(name, n):
+        sd[name + ".weight"] = f32(rng.uniform(0.6, 1.4, n))
+        sd[name + ".bias"] = f32(rng.standard_normal(n) * 0.1)
+
+    def linear(name, nout, nin, gain=1.0):
+        sd[name + ".weight"] = f32(rng.standard_normal((nout, nin)) * gain / np.sqrt(nin))
+        sd[name + ".bias"] = f32(rng.standard_normal(nout) * 0.1)
+
+    sd["embeddings.word_embeddings.weight"] = f32(rng.standard_normal((cfg["vocab_size"], D)) * 0.5)
+    sd["embeddings.position_embeddings.weight"] = f32(rng.standard_normal((cfg["max_position_embeddings"], D)) * 0.5)
+    sd["embeddings.token_type_embeddings.weight"] = f32(rng.standard_normal((cfg.get("type_vocab_size", 2), D)) * 0.5)
+    norm("embeddings.LayerNorm", D)
+    for i in range(cfg["num_hidden_layers"]):
+        p = "encoder.layer.%d." % i
+        linear(p + "attention.self.query", D, D, 2.0)
+        linear(p + "attention.self.key", D, D, 2.0)
+        linear(p + "attention.self.value", D, D)
+        linear(p + "attention.output.dense", D, D)
+        norm(p + "attention.output.LayerNorm", D)
+        linear(p + "intermediate.dense", F, D)
+        linear(p + "output.dense", D, F)
+        norm(p + "output.LayerNorm", D)
+    return sd
+
+
+def make_vocab():
+    """A 97-entry vocab.txt word list (BERT_TINY's vocab_size): the five specials, punctuation, single letters and
+    digits as whole words and as ## pieces, a few words and pieces, one accented-stripped word and one CJK character."""
+    words = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]", ".", ",", "!", "?", "'", "-", "(", ")"]
+    words += list("abcdefghijklmnopqrstuvwxyz")
+    words += ["##" + c for c in "abcdefghijklmnopqrstuvwxyz"]
+    words += ["the", "and", "you", "so", "is", "it", "to", "of", "hello", "world", "gesture", "speak", "hand", "we",
+              "un", "##ing", "##ed", "##er", "##ly", "##able", "cafe", "naive", "Hello", "The", "I",
+              "中", "文", "0", "1", "2", "##0", "##1"]
+    assert len(words) == 97 and len(set(words)) == 97
+    return words
