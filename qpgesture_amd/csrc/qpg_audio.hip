@@ -18,6 +18,8 @@
 //   128-B runs along the candidate axis of D[q][c].
 #include "qpg_common.h"
 
+#include <type_traits>
+
 __global__ __launch_bounds__(1024) void audio_pack_queries_kernel(const float* __restrict__ qbase, int M, int T, int F,
                                                                   const int32_t* __restrict__ q_win,
                                                                   const int32_t* __restrict__ q_t, int n_taps,
@@ -75,6 +77,40 @@ extern "C" int qpg_audio_pack_queries(qpg_ctx* ctx, void* stream, const float* q
   return QPG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// What the three sweeps below share: their arguments, the row of a lane on either side, the padded-tap rule, the
+// split-K operand loads, stage issue pattern and reduction, and the epilogue of one (query, candidate) pair.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int NTAPS = 6;  // frames of a candidate; the tap schedules of the k loops are written out for six
+// Waves of a split-K block (one per SIMD): each takes a quarter of the feature axis.  An 8-wave split (finer work units,
+// 6.5 instead of 3.25 rounds of blocks at N_db=2048) measured slower on MI355X: 703 vs 629 us (r01 notes).
+constexpr int KS = 4;
+constexpr int MPL = 2;    // MFMAs named in front of every load of a split-K stage
+
+template <int S>
+struct IC {               // a stage number that a generic lambda can use as a constant
+  static constexpr int value = S;
+};
+
+struct AudioArgs {
+  const void* base;       // [N][T][F] the track: f32, or IEEE f16 in the kernels instantiated with HALF
+  int N, T, F;
+  const int32_t* cand_t;  // [G] first frame of every candidate of a window
+  int G, tap_stride;      // candidate c = window c / G, frames cand_t[c % G] + tap * tap_stride
+  const double* cn2;      // [N][G] squared norms of the candidates
+  const float* q32;       // [Q][NTAPS * F] the packed queries (audio_pack_queries_kernel)
+  const double* qn2;      // [Q] their squared norms
+  int Q;
+  int d_f32;              // D holds f32 (else f64)
+  void* D;                // [Q][ldD] the distances
+  int64_t ldD;
+  const float* zeros;     // the context's zero page: what a tap at or past T reads
+  int32_t* stats;         // the mixed sweeps' flag word ([1] |= 2: operand products may underflow f32); NULL: no flag
+  int64_t c_begin, c_end; // candidates [c_begin, c_end) of the N * G
+  int main_blocks;        // mx2: blocks past this many are split-K blocks over the candidates [c_end, c_tail_end)
+  int64_t c_tail_end;
+};
+
 // Wave tile = MT*16 candidates x NT*16 queries.  Per (e0, tap) a lane loads MT + NT float4 (16 B each;
 // the query operand is kept in f32 in memory — WavLM values are f32 — and widened in registers) and
 // issues 4*MT*NT MFMAs, i.e. (MT+NT)*16 B of L1/L2 traffic per 4*MT*NT*64 matrix-pipe cycles.  At
@@ -84,44 +120,156 @@ extern "C" int qpg_audio_pack_queries(qpg_ctx* ctx, void* stream, const float* q
 // features, widened f16 -> f32 -> f64 in registers; the arithmetic is the same f64 as for an f32 base, applied to the
 // f16-rounded values (so results match the oracle run on the rounded track, not on the original one).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <int MT, int NT, int NTAPS, int KS, bool HALF>
-__global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* __restrict__ base_, int N, int T, int F,
-                                                               const int32_t* __restrict__ cand_t, int G,
-                                                               int tap_stride, const double* __restrict__ cn2,
-                                                               const float* __restrict__ q32,
-                                                               const double* __restrict__ qn2, int Q,
-                                                               double* __restrict__ D, int64_t ldD,
-                                                               const float* __restrict__ zeros, int64_t c_begin,
-                                                               int64_t c_end) {
+
+// Candidate c of the launch, clamped to its last one (stores are masked): its first frame and the element offset of
+// that frame's features in the track.
+struct CandRow {
+  int t0;
+  int64_t off;
+};
+__device__ __forceinline__ CandRow cand_row(const AudioArgs& A, int64_t c) {
+  if (c >= A.c_end) c = A.c_end - 1;
+  const int j = (int)(c / A.G), g = (int)(c - (int64_t)j * A.G);
+  const int t0 = A.cand_t[g];
+  return {t0, ((int64_t)j * A.T + t0) * A.F};
+}
+
+// Packed row of query q, clamped to the last one (stores are masked).
+__device__ __forceinline__ const float* query_row(const AudioArgs& A, int q) {
+  if (q >= A.Q) q = A.Q - 1;
+  return A.q32 + (int64_t)q * (NTAPS * A.F);
+}
+
+template <bool HALF>
+using track_t = std::conditional_t<HALF, _Float16, float>;
+
+// Where feature e0 of tap `tap` of a candidate row is read from; row + off is the lane's place in the row's first frame t0.
+// Taps past the end of the window are zero padding (data_processing.py:266): the load is unconditional (a conditional
+// load makes hipcc branch around it and drain vmcnt(0), which serialises the prefetch) and a padded tap reads the
+// context's zero page instead of being selected to zero afterwards.
+template <typename E>
+struct TapSrc {
+  const E* p;
+  bool in_track;
+};
+template <typename E>
+__device__ __forceinline__ TapSrc<E> tap_src(const AudioArgs& A, const E* row, int64_t off, int t0, int tap, int e0) {
+  const bool ok = t0 + tap * A.tap_stride < A.T;
+  const E* p = row + off + (int64_t)tap * A.tap_stride * A.F + e0;
+  return {ok ? p : reinterpret_cast<const E*>(A.zeros), ok};
+}
+
+__device__ __forceinline__ void load8(const float* p, f32x4 (&v)[2]) {
+  v[0] = *reinterpret_cast<const f32x4*>(p);
+  v[1] = *reinterpret_cast<const f32x4*>(p + 4);
+}
+
+// The 8 features from e0 on of tap `tap` of MT candidate rows (element offsets aoff, first frames at0), widened to f32, and
+// of NT query rows: one split-K operand buffer each.
+template <int MT, bool HALF>
+__device__ __forceinline__ void ks_load_cand(const AudioArgs& A, const int64_t (&aoff)[MT], const int (&at0)[MT], int e0,
+                                             int tap, f32x4 (&a)[MT][2]) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const track_t<HALF>* p = tap_src(A, static_cast<const track_t<HALF>*>(A.base), aoff[mt], at0[mt], tap, e0).p;
+    if constexpr (HALF) {      // f16 base: one 16-byte load brings the lane's 8 features
+      const f16x8 h = *reinterpret_cast<const f16x8*>(p);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        a[mt][0][i] = (float)h[i];
+        a[mt][1][i] = (float)h[4 + i];
+      }
+    } else {
+      load8(p, a[mt]);
+    }
+  }
+}
+template <int NT>
+__device__ __forceinline__ void ks_load_query(const AudioArgs& A, const float* const (&brow)[NT], int e0, int tap,
+                                              f32x4 (&b)[NT][2]) {
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) load8(brow[nt] + tap * A.F + e0, b[nt]);
+}
+
+// Issue pattern of one (load next group, 8*MT*NT MFMAs of the current group) stage: the (MT+NT)*2 16-B loads are
+// spread between the MFMAs — 2 MFMAs, 1 load, ... — instead of being issued as one burst in front of them, so the
+// matrix pipe is never left waiting behind a queue of address computations and the loads still lead their use by
+// a whole stage.  sched_barrier(0) closes the region.
+template <int MT, int NT>
+__device__ __forceinline__ void ks_stage_issue() {
+#pragma unroll
+  for (int sg = 0; sg < (MT + NT) * 2; ++sg) {
+    __builtin_amdgcn_sched_group_barrier(0x008, MPL, 0);
+    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+  }
+  __builtin_amdgcn_sched_group_barrier(0x008, 8 * MT * NT - MPL * 2 * (MT + NT), 0);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Epilogue of one pair: the distance from the dot product and the two squared norms (a = qn2[q], which the caller may
+// hold for several pairs), stored as D says.  Operand products that underflow f32 would break the mixed sweeps' bound:
+// |q||c| < 1e-16 raises the flag.  EXACT: the f64 sweep, which has no flag to raise and no f32 form of D.
+template <bool EXACT>
+__device__ __forceinline__ void store_pair(const AudioArgs& A, int q, int64_t cc, double dot, double a) {
+  const double b = A.cn2[cc];
+  const double p = a * b;
+  if (!EXACT && p > 0.0 && p < 1e-32 && A.stats) atomicOr(&A.stats[1], 2);
+  const double dd = cosine_from_dot(dot, a, b);
+  if (!EXACT && A.d_f32) static_cast<float*>(A.D)[(int64_t)q * A.ldD + cc] = (float)dd;
+  else static_cast<double*>(A.D)[(int64_t)q * A.ldD + cc] = dd;
+}
+
+// The partial sums of the KS waves are reduced through LDS, turned into distances and stored.  Output element
+// o = ql*(16*MT) + cr (query-local, candidate row): consecutive threads walk the candidate axis, so each query row gets
+// one (128*MT)-B store run.  EXACT names the sweep and with it the C/D layout of the sums: lane l, reg r holds query col
+// l&15 and candidate row   v_mfma_f64_16x16x4_f64 (EXACT): (l>>4) + 4r        v_mfma_f32_16x16x4_f32: 4*(l>>4) + r
+template <int MT, int NT, bool EXACT>
+__device__ __forceinline__ void ks_reduce_store(const AudioArgs& A, const double (&red)[KS][MT * NT][4][64], int64_t c0, int q0) {
+  __syncthreads();
+
+  constexpr int CR = 16 * MT;
+  for (int o = threadIdx.x; o < NT * 16 * CR; o += 64 * KS) {
+    const int ql = o / CR, cr = o - ql * CR;
+    const int nt = ql >> 4, qc = ql & 15;
+    const int mt = cr >> 4, crr = cr & 15;
+    const int r = EXACT ? crr >> 2 : crr & 3, l = ((EXACT ? crr & 3 : crr >> 2) << 4) | qc;
+    const int t = mt * NT + nt;
+    double dot = red[0][t][r][l];
+#pragma unroll
+    for (int k = 1; k < KS; ++k) dot += red[k][t][r][l];
+    const int q = q0 + ql;
+    const int64_t cc = c0 + cr;
+    if (q < A.Q && cc < A.c_end) store_pair<EXACT>(A, q, cc, dot, A.qn2[q]);
+  }
+}
+
+// The exact sweep: split-K blocks of MT = 2 tiles throughout, no stats word, f64 matrix.  The LDS-shared-query organisation
+// of the mixed sweep for whole rounds of blocks was NOT faster for f64: at 64 cycles per MFMA the split-K kernel is already
+// at the matrix pipe's pace (MI355X: 594 vs 590 us at Q = 48, 0.83 vs 0.81 of the roof at Q = 768, 0.79 vs 0.76 ms per step).
+template <int NT, bool HALF>
+__global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const AudioArgs A) {
+  constexpr int MT = 2;
   __shared__ double red[KS][MT * NT][4][64];  // [wave][tile][acc reg][lane]
 
-  const int64_t C = c_end;                     // candidates [c_begin, c_end) of the N*G
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = lane & 15, kq = lane >> 4;
-  const int64_t c0 = c_begin + (int64_t)blockIdx.x * (16 * MT);
+  const int64_t c0 = A.c_begin + (int64_t)blockIdx.x * (16 * MT);
   const int q0 = blockIdx.y * (NT * 16);
 
   // A side: this lane's candidate row in each of the MT tiles (element offsets into the base track)
-  const float* base = static_cast<const float*>(base_);
-  const _Float16* baseh = static_cast<const _Float16*>(base_);
   int64_t aoff[MT];
   int at0[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    int64_t c = c0 + mt * 16 + row;
-    if (c >= C) c = C - 1;
-    const int j = (int)(c / G), g = (int)(c - (int64_t)j * G);
-    at0[mt] = cand_t[g];
-    aoff[mt] = ((int64_t)j * T + at0[mt]) * F + 8 * kq;
+    const CandRow cr = cand_row(A, c0 + mt * 16 + row);
+    at0[mt] = cr.t0;
+    aoff[mt] = cr.off + 8 * kq;
   }
   // B side: this lane's query column in each of the NT tiles
-  const int KQ = NTAPS * F;
   const float* brow[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    int q = q0 + nt * 16 + row;
-    if (q >= Q) q = Q - 1;
-    brow[nt] = q32 + (int64_t)q * KQ + 8 * kq;
+    brow[nt] = query_row(A, q0 + nt * 16 + row) + 8 * kq;
   }
 
   f64x4 acc[MT][NT];
@@ -138,33 +286,8 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
     f32x4 a[MT][2], b[NT][2];
   };
   auto load = [&](Buf& u, int e0, int tap) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      // taps past the end of the window are zero padding (data_processing.py:266): the load is unconditional (a
-      // conditional load makes hipcc branch around it and drain vmcnt(0), which serialises the prefetch) and a
-      // padded tap reads the context's zero page instead of being selected to zero afterwards
-      const bool ok = at0[mt] + tap * tap_stride < T;
-      const int64_t o = aoff[mt] + (int64_t)tap * tap_stride * F + e0;
-      if (HALF) {
-        const f16x8 h = *reinterpret_cast<const f16x8*>(ok ? reinterpret_cast<const void*>(baseh + o)
-                                                           : reinterpret_cast<const void*>(zeros));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          u.a[mt][0][i] = (float)h[i];
-          u.a[mt][1][i] = (float)h[4 + i];
-        }
-      } else {
-        const float* p = ok ? base + o : zeros;
-        u.a[mt][0] = *reinterpret_cast<const f32x4*>(p);
-        u.a[mt][1] = *reinterpret_cast<const f32x4*>(p + 4);
-      }
-    }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const float* p = brow[nt] + tap * F + e0;
-      u.b[nt][0] = *reinterpret_cast<const f32x4*>(p);
-      u.b[nt][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
+    ks_load_cand<MT, HALF>(A, aoff, at0, e0, tap, u.a);
+    ks_load_query(A, brow, e0, tap, u.b);
   };
   auto mma = [&](const Buf& u) {
 #pragma unroll
@@ -184,34 +307,23 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
       }
   };
 
-  static_assert(NTAPS == 6, "tap schedule below is written for 6 taps");
-  const int eBeg = w * (F / KS), eEnd = eBeg + (F / KS);
+  const int eBeg = w * (A.F / KS), eEnd = eBeg + (A.F / KS);
   Buf u0, u1;
   load(u0, eBeg, 0);
-  // Issue pattern of one (load next group, 8*MT*NT MFMAs of the current group) stage: the (MT+NT)*2 16-B loads are
-  // spread between the MFMAs — 2 MFMAs, 1 load, ... — instead of being issued as one burst in front of them, so the
-  // matrix pipe is never left waiting behind a queue of address computations and the loads still lead their use by
-  // a whole stage.  sched_barrier(0) closes the region.
-#define QPG_MPL 2         // MFMAs named in front of every load of a stage
-#define QPG_AUDIO_STAGE(LOADSTMT, MMASTMT)                                   \
-  LOADSTMT;                                                                  \
-  MMASTMT;                                                                   \
-  _Pragma("unroll") for (int sg = 0; sg < (MT + NT) * 2; ++sg) {             \
-    __builtin_amdgcn_sched_group_barrier(0x008, QPG_MPL, 0);                 \
-    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                       \
-  }                                                                          \
-  __builtin_amdgcn_sched_group_barrier(0x008, 8 * MT * NT - QPG_MPL * 2 * (MT + NT), 0); \
-  __builtin_amdgcn_sched_barrier(0);
+  auto stage = [&](Buf& next, int e0, int tap, const Buf& cur) {
+    load(next, e0, tap);
+    mma(cur);
+    ks_stage_issue<MT, NT>();
+  };
   for (int e0 = eBeg; e0 < eEnd; e0 += 32) {
-    QPG_AUDIO_STAGE(load(u1, e0, 1), mma(u0))
-    QPG_AUDIO_STAGE(load(u0, e0, 2), mma(u1))
-    QPG_AUDIO_STAGE(load(u1, e0, 3), mma(u0))
-    QPG_AUDIO_STAGE(load(u0, e0, 4), mma(u1))
-    QPG_AUDIO_STAGE(load(u1, e0, 5), mma(u0))
+    stage(u1, e0, 1, u0);
+    stage(u0, e0, 2, u1);
+    stage(u1, e0, 3, u0);
+    stage(u0, e0, 4, u1);
+    stage(u1, e0, 5, u0);
     const int en = (e0 + 32 < eEnd) ? e0 + 32 : eBeg;   // last prefetch wraps to a valid address, unused
-    QPG_AUDIO_STAGE(load(u0, en, 0), mma(u1))
+    stage(u0, en, 0, u1);
   }
-#undef QPG_AUDIO_STAGE
 
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -222,28 +334,7 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
       red[w][mt * NT + nt][2][lane] = acc[mt][nt].z;
       red[w][mt * NT + nt][3][lane] = acc[mt][nt].w;
     }
-  __syncthreads();
-
-  // f64 C/D layout of v_mfma_f64_16x16x4_f64: lane l, reg r holds (cand row = (l>>4) + 4r, query col = l&15).
-  // Output element o = ql*(16*MT) + cr (query-local, candidate row): consecutive threads walk the
-  // candidate axis, so each query row gets one (128*MT)-B store run.
-  constexpr int CR = 16 * MT;
-  for (int o = threadIdx.x; o < NT * 16 * CR; o += 64 * KS) {
-    const int ql = o / CR, cr = o - ql * CR;
-    const int nt = ql >> 4, qc = ql & 15;
-    const int mt = cr >> 4, crr = cr & 15;
-    const int r = crr >> 2, l = ((crr & 3) << 4) | qc;
-    const int t = mt * NT + nt;
-    double dot = red[0][t][r][l];
-#pragma unroll
-    for (int k = 1; k < KS; ++k) dot += red[k][t][r][l];
-    const int q = q0 + ql;
-    const int64_t cc = c0 + cr;
-    if (q < Q && cc < C) {
-      const double d = cosine_from_dot(dot, qn2[q], cn2[cc]);
-      D[(int64_t)q * ldD + cc] = d;
-    }
-  }
+  ks_reduce_store<MT, NT, true>(A, red, c0, q0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -254,54 +345,40 @@ __global__ __launch_bounds__(64 * KS) void audio_cosine_f64_kernel(const void* _
 //   * an f32 FMA chain of n products has |error| <= gamma_n * sum|a_i b_i| <= gamma_n |a||b| (Cauchy-Schwarz), any
 //     summation order, gamma_n = n u / (1 - n u), u = 2^-24; the f64 sums add < 1e-13 relative;
 //   => |D_mx - D_exact| <= gamma_32 + 1e-13 < 1.92e-6 for every (query, candidate), data independent; + 1.2e-7 when
-//      the matrix is stored in f32 (distances <= 2): QPG_AUDIO_MX_ERR = 2.05e-6 covers both forms
-//      (QPG_AUDIO_MX_ERR below; tests/test_gpu_matching.py measures the actual maximum, ~1e-7).
+//      the matrix is stored in f32 (distances <= 2): QPG_AUDIO_MX_ERR = 2.05e-6 of include/qpg.h covers both forms
+//      (tests/test_gpu_matching.py measures the actual maximum, ~1e-7).
 // qpg_percode_select_mixed_f64 consumes this matrix: every comparison that decides an output (per-code minimum,
 // rank order of the minima) and whose operands are closer than 2*QPG_AUDIO_MX_ERR is re-evaluated with an f64 dot
 // product first and, when still closer than the near-tie eps, in the reference's own arithmetic.  Operand products
 // that underflow f32 would break the bound: a pair with 0 < |q||c| < 1e-16 raises stats[1] |= 2.
 // ---------------------------------------------------------------------------------------------------------------
-#define QPG_MX_OCC 1      // waves per SIMD the register allocation is held to
-template <int S>
-struct MxIC {
-  static constexpr int value = S;
-};
-// AD = depth of the candidate-operand register ring: the candidate rows come from HBM (~2k cycles away under load)
-// and are prefetched AD-1 stages (of 8*MT*NT MFMAs = 256*MT*NT matrix-pipe cycles) ahead; the query operand sits in
-// the XCD's L2 (the whole query set is 1.2 MB) and is prefetched one stage ahead.
-template <int MT, int NT, int NTAPS, int KS, int GS, int AD, int BD, bool HALF = false>
-__device__ __forceinline__ void mx_ksplit_body(
-    const float* __restrict__ base, int N, int T, int F, const int32_t* __restrict__ cand_t, int G, int tap_stride,
-    const double* __restrict__ cn2, const float* __restrict__ q32, const double* __restrict__ qn2, int Q,
-    double* __restrict__ D, int64_t ldD, const float* __restrict__ zeros, int32_t* __restrict__ stats, int64_t c_begin,
-    int64_t c_end, const unsigned bx, const unsigned by, const int d_f32) {
-  // candidates [c_begin, c_end) of the N*G; block = GS candidate groups x KS contraction slices (one wave each); the KS waves of a group are reduced through LDS
-  __shared__ double red[GS][KS][MT * NT][4][64];  // [group][slice][tile][acc reg][lane]
+constexpr int MX_OCC = 1;   // waves per SIMD the split-K register allocation is held to
+// Both operands go through register rings of depth RING and are requested RING-1 stages (of 8*MT*NT MFMAs = 256*MT*NT
+// matrix-pipe cycles) ahead: the candidate rows come from HBM (~2k cycles away under load), the query operand sits in the
+// XCD's L2 (the whole query set is 1.2 MB).
+template <int MT, int NT, bool HALF>
+__device__ __forceinline__ void mx_ksplit_body(const AudioArgs A, const unsigned bx, const unsigned by) {
+  constexpr int RING = 2;
+  // candidates [c_begin, c_end) of the N*G; block (bx, by) = one tile, KS contraction slices (one wave each), reduced through LDS
+  __shared__ double red[KS][MT * NT][4][64];  // [slice][tile][acc reg][lane]
 
-  const int64_t C = c_end;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int w = wave % KS, gs = wave / KS;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = lane & 15, kq = lane >> 4;
-  const int64_t c0 = c_begin + ((int64_t)bx * GS + gs) * (16 * MT);
+  const int64_t c0 = A.c_begin + (int64_t)bx * (16 * MT);
   const int q0 = by * (NT * 16);
 
   int64_t aoff[MT];
   int at0[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    int64_t c = c0 + mt * 16 + row;
-    if (c >= C) c = C - 1;
-    const int j = (int)(c / G), g = (int)(c - (int64_t)j * G);
-    at0[mt] = cand_t[g];
-    aoff[mt] = ((int64_t)j * T + at0[mt]) * F + 8 * kq;
+    const CandRow cr = cand_row(A, c0 + mt * 16 + row);
+    at0[mt] = cr.t0;
+    aoff[mt] = cr.off + 8 * kq;
   }
-  const int KQ = NTAPS * F;
   const float* brow[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    int q = q0 + nt * 16 + row;
-    if (q >= Q) q = Q - 1;
-    brow[nt] = q32 + (int64_t)q * KQ + 8 * kq;
+    brow[nt] = query_row(A, q0 + nt * 16 + row) + 8 * kq;
   }
 
   f64x4 sum[MT][NT];
@@ -320,34 +397,8 @@ __device__ __forceinline__ void mx_ksplit_body(
   struct BufB {
     f32x4 b[NT][2];
   };
-  auto loadA = [&](BufA& u, int e0, int tap) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const bool ok = at0[mt] + tap * tap_stride < T;          // padded taps read the zero page (see the f64 kernel)
-      const int64_t o = aoff[mt] + (int64_t)tap * tap_stride * F + e0;
-      if (HALF) {      // f16 base: one 16-byte load brings the lane's 8 features
-        const f16x8 h = *reinterpret_cast<const f16x8*>(ok ? reinterpret_cast<const void*>(reinterpret_cast<const _Float16*>(base) + o)
-                                                           : reinterpret_cast<const void*>(zeros));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          u.a[mt][0][i] = (float)h[i];
-          u.a[mt][1][i] = (float)h[4 + i];
-        }
-        continue;
-      }
-      const float* p = ok ? base + o : zeros;
-      u.a[mt][0] = *reinterpret_cast<const f32x4*>(p);
-      u.a[mt][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-  };
-  auto loadB = [&](BufB& u, int e0, int tap) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const float* p = brow[nt] + tap * F + e0;
-      u.b[nt][0] = *reinterpret_cast<const f32x4*>(p);
-      u.b[nt][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-  };
+  auto loadA = [&](BufA& u, int e0, int tap) { ks_load_cand<MT, HALF>(A, aoff, at0, e0, tap, u.a); };
+  auto loadB = [&](BufB& u, int e0, int tap) { ks_load_query(A, brow, e0, tap, u.b); };
   // one stage: the finished 32-product chain of every tile goes into its f64 sum, then a fresh chain starts from C = 0
   auto mma = [&](const BufA& ua, const BufB& ub) {
 #pragma unroll
@@ -368,11 +419,8 @@ __device__ __forceinline__ void mx_ksplit_body(
           }
   };
 
-  static_assert(NTAPS == 6, "tap schedule below is written for 6 taps");
-  static_assert(AD >= 2 && AD <= 4 && BD >= 2 && BD <= 3, "ring depths");
-  constexpr int L = (AD == 4) ? 12 : 6;                 // stages per unrolled super-iteration (multiple of AD, BD, 6)
-  const int eBeg = w * (F / KS);
-  const int ne = (F / KS) / 32;                         // feature groups of 32 per wave; stage s = (group s/6, tap s%6)
+  const int eBeg = w * (A.F / KS);
+  const int ne = (A.F / KS) / 32;                       // feature groups of 32 per wave; stage s = (group s/6, tap s%6)
   const int nst = NTAPS * ne;
   // blocks start their walk over the feature groups at different offsets: all blocks read the SAME query rows, and in
   // lockstep they would all hit the same few L2 channels at any moment (only the order of the f64 additions changes)
@@ -383,39 +431,27 @@ __device__ __forceinline__ void mx_ksplit_body(
     g = g >= ne ? g - ne : g;
     return eBeg + 32 * g;
   };
-  BufA ra[AD];
-  BufB rb[BD];
+  BufA ra[RING];
+  BufB rb[RING];
 #pragma unroll
-  for (int d = 0; d < BD - 1; ++d) loadB(rb[d], eof((d / 6) % ne), d % 6);
+  for (int d = 0; d < RING - 1; ++d) loadB(rb[d], eof((d / NTAPS) % ne), d % NTAPS);
 #pragma unroll
-  for (int d = 0; d < AD - 1; ++d) loadA(ra[d], eof((d / 6) % ne), d % 6);
-#define QPG_MX_MPL 2      // MFMAs named in front of every load of a stage
-  for (int s0 = 0; s0 < nst; s0 += L) {
-    const int g0 = s0 / 6;
+  for (int d = 0; d < RING - 1; ++d) loadA(ra[d], eof((d / NTAPS) % ne), d % NTAPS);
+  for (int s0 = 0; s0 < nst; s0 += NTAPS) {
+    const int g0 = s0 / NTAPS;
     auto stage = [&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      constexpr int ja = j + AD - 1, jb = j + BD - 1;
-      int ga = g0 + ja / 6, gb = g0 + jb / 6;           // prefetches past the end wrap to a valid address, unused
-      ga = ga >= ne ? ga - ne : ga;
-      ga = ga >= ne ? 0 : ga;
-      gb = gb >= ne ? gb - ne : gb;
-      gb = gb >= ne ? 0 : gb;
+      constexpr int jn = j + RING - 1;                  // the stage requested under this one's MFMAs
+      int gn = g0 + jn / NTAPS;                         // prefetches past the end wrap to a valid address, unused
+      gn = gn >= ne ? gn - ne : gn;
+      gn = gn >= ne ? 0 : gn;
       // query loads first: the wait for them at the next stage must not also wait for the (younger, slower) HBM loads
-      loadB(rb[jb % BD], eof(gb), jb % 6);
-      loadA(ra[ja % AD], eof(ga), ja % 6);
-      mma(ra[j % AD], rb[j % BD]);
-#pragma unroll
-      for (int sg = 0; sg < (MT + NT) * 2; ++sg) {
-        __builtin_amdgcn_sched_group_barrier(0x008, QPG_MX_MPL, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 8 * MT * NT - QPG_MX_MPL * 2 * (MT + NT), 0);
-      __builtin_amdgcn_sched_barrier(0);
+      loadB(rb[jn % RING], eof(gn), jn % NTAPS);
+      loadA(ra[jn % RING], eof(gn), jn % NTAPS);
+      mma(ra[j % RING], rb[j % RING]);
+      ks_stage_issue<MT, NT>();
     };
-    stage(MxIC<0>{}); stage(MxIC<1>{}); stage(MxIC<2>{}); stage(MxIC<3>{}); stage(MxIC<4>{}); stage(MxIC<5>{});
-    if constexpr (L == 12) {
-      stage(MxIC<6>{}); stage(MxIC<7>{}); stage(MxIC<8>{}); stage(MxIC<9>{}); stage(MxIC<10>{}); stage(MxIC<11>{});
-    }
+    stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{}); stage(IC<3>{}); stage(IC<4>{}); stage(IC<5>{});
   }
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -424,42 +460,14 @@ __device__ __forceinline__ void mx_ksplit_body(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         sum[mt][nt][r] += (double)acc[mt][nt][r];
-        red[gs][w][mt * NT + nt][r][lane] = sum[mt][nt][r];
+        red[w][mt * NT + nt][r][lane] = sum[mt][nt][r];
       }
-  __syncthreads();
-
-  // C/D layout of v_mfma_f32_16x16x4_f32: lane l, reg r holds (cand row = 4*(l>>4) + r, query col = l&15)
-  constexpr int CR = 16 * MT;
-  for (int o = threadIdx.x - gs * 64 * KS; o < NT * 16 * CR; o += 64 * KS) {
-    const int ql = o / CR, cr = o - ql * CR;
-    const int nt = ql >> 4, qc = ql & 15;
-    const int mt = cr >> 4, crr = cr & 15;
-    const int r = crr & 3, l = ((crr >> 2) << 4) | qc;
-    const int t = mt * NT + nt;
-    double dot = red[gs][0][t][r][l];
-#pragma unroll
-    for (int k = 1; k < KS; ++k) dot += red[gs][k][t][r][l];
-    const int q = q0 + ql;
-    const int64_t cc = c0 + cr;
-    if (q < Q && cc < C) {
-      const double a = qn2[q], b = cn2[cc];
-      const double p = a * b;
-      if (p > 0.0 && p < 1e-32 && stats) atomicOr(&stats[1], 2);     // |q||c| < 1e-16: f32 products may underflow
-      const double dd = cosine_from_dot(dot, a, b);
-      if (d_f32) reinterpret_cast<float*>(D)[(int64_t)q * ldD + cc] = (float)dd;
-      else D[(int64_t)q * ldD + cc] = dd;
-    }
-  }
+  ks_reduce_store<MT, NT, false>(A, red, c0, q0);
 }
 
-template <int MT, int NT, int NTAPS, int KS, int GS, int AD, int BD, bool HALF>
-__global__ __launch_bounds__(64 * KS * GS, QPG_MX_OCC) void audio_cosine_mx_kernel(
-    const float* __restrict__ base, int N, int T, int F, const int32_t* __restrict__ cand_t, int G, int tap_stride,
-    const double* __restrict__ cn2, const float* __restrict__ q32, const double* __restrict__ qn2, int Q,
-    double* __restrict__ D, int64_t ldD, const float* __restrict__ zeros, int32_t* __restrict__ stats, int64_t c_begin,
-    int64_t c_end, int d_f32) {
-  mx_ksplit_body<MT, NT, NTAPS, KS, GS, AD, BD, HALF>(base, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, zeros, stats,
-                                                c_begin, c_end, blockIdx.x, blockIdx.y, d_f32);
+template <int MT, int NT, bool HALF>
+__global__ __launch_bounds__(64 * KS, MX_OCC) void audio_cosine_mx_kernel(const AudioArgs A) {
+  mx_ksplit_body<MT, NT, HALF>(A, blockIdx.x, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -473,26 +481,20 @@ __global__ __launch_bounds__(64 * KS * GS, QPG_MX_OCC) void audio_cosine_mx_kern
 // buffers.  f32 chains are still cut every 32 products (two flushes per stage), so QPG_AUDIO_MX_ERR holds.
 // ---------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* mx_lds_ptr_t;
-typedef __attribute__((address_space(1))) const void* mx_gbl_ptr_t;
-#define QPG_MX2_OCC 2     // waves per SIMD the register allocation is held to
-// row -> XOR applied to the 16-byte slot index of its 256-byte LDS row.  A ds_read_b128 lane group is 16 rows, eight
+constexpr int MX2_OCC = 2;  // waves per SIMD the register allocation is held to
+// The 16-byte slot index of a piece inside its 256-byte LDS row is XORed with the row number.  A ds_read_b128 lane group is 16 rows, eight
 // of them ({0-3,12-15} or {4-11}) at k-quarter kq and the other eight at kq^1, all reading sub-piece 4*i + kq: with
 // slot = piece ^ row both eights land on disjoint slot sets ({4..11} is closed under ^1), i.e. conflict-free.
-__device__ __forceinline__ int mx2_g(int r) { return r; }
-
-// F64 = true: the SAME organisation on the f64 matrix cores (v_mfma_f64_16x16x4_f64, operands widened in registers, no
-// chains to cut).  No launch instantiates it: for the f64 sweep it measured no faster than split-K (see audio_cosine()).
-template <int NT, int NTAPS, bool F64, bool HALF>
-__global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
-    const float* __restrict__ base, int N, int T, int F, const int32_t* __restrict__ cand_t, int G, int tap_stride,
-    const double* __restrict__ cn2, const float* __restrict__ q32, const double* __restrict__ qn2, int Q,
-    double* __restrict__ D, int64_t ldD, const float* __restrict__ zeros, int32_t* __restrict__ stats, int64_t c_begin,
-    int64_t c_end, int main_blocks, int64_t c_tail_end, int d_f32) {
+template <bool HALF>
+__global__ __launch_bounds__(256, MX2_OCC) void audio_cosine_mx2_kernel(const AudioArgs A) {
+  constexpr int NT = 3;                           // query tiles of a block: 48 queries
   // blocks past `main_blocks` are the split-K remainder (one 16-candidate tile each, candidates from c_end on): they
   // ride in the same launch so that they fill the CUs while the last round of 64-candidate blocks drains
-  if (!F64 && blockIdx.x >= (unsigned)main_blocks) {
-    mx_ksplit_body<1, NT, NTAPS, 4, 1, 2, 2, HALF>(base, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, zeros,
-                                                   stats, c_end, c_tail_end, blockIdx.x - (unsigned)main_blocks, blockIdx.y, d_f32);
+  if (blockIdx.x >= (unsigned)A.main_blocks) {
+    AudioArgs tail = A;
+    tail.c_begin = A.c_end;
+    tail.c_end = A.c_tail_end;
+    mx_ksplit_body<1, NT, HALF>(tail, blockIdx.x - (unsigned)A.main_blocks, blockIdx.y);
     return;
   }
   constexpr int ROWB = 256;                       // bytes of one query row per stage (64 features)
@@ -502,47 +504,41 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = lane & 15, kq = lane >> 4;
-  const int64_t c0 = c_begin + ((int64_t)blockIdx.x * 4 + w) * 16;
+  const int64_t c0 = A.c_begin + ((int64_t)blockIdx.x * 4 + w) * 16;
   const int q0 = blockIdx.y * (NT * 16);
-  const int KQ = NTAPS * F;
 
   // candidate row of this lane (clamped; stores are masked)
-  int64_t c = c0 + row;
-  if (c >= c_end) c = c_end - 1;
-  const int j = (int)(c / G), g = (int)(c - (int64_t)j * G);
-  const int at0 = cand_t[g];
+  const CandRow cr = cand_row(A, c0 + row);
+  const int at0 = cr.t0;
   // feature of (load i, k-quarter kq, element e) within a stage = 16*i + 4*kq + e: the four lanes of a row cover 64
   // contiguous bytes per load instruction (16 half lines per instruction; 16*kq + 4*i would touch 32)
   // f16 base (HALF): the lane's 16 features of a stage are two contiguous runs of 8 (one 16-byte load each):
   // feature of (i, kq, e) = 32*(i>>1) + 8*kq + 4*(i&1) + e, and the query fragments follow that order (boff below)
-  const int64_t arow_off = ((int64_t)j * T + at0) * F + (HALF ? 8 : 4) * kq;
-  const float* arow = base + arow_off;
-  const _Float16* arow_h = reinterpret_cast<const _Float16*>(base) + arow_off;
+  const int64_t arow_off = cr.off + (HALF ? 8 : 4) * kq;
+  const track_t<HALF>* arow = static_cast<const track_t<HALF>*>(A.base) + arow_off;
   // DMA source rows of this lane: piece pi covers tile rows 4*pi .. 4*pi+3, lane l -> row 4*pi + (l>>4), slot l&15
   const float* dsrc[PIECES / 4];
 #pragma unroll
   for (int i = 0; i < PIECES / 4; ++i) {
     const int pi = w + 4 * i;
     const int R = 4 * pi + (lane >> 4);
-    int q = q0 + R;
-    if (q >= Q) q = Q - 1;
-    const int p = (lane & 15) ^ mx2_g(R & 15);
-    dsrc[i] = q32 + (int64_t)q * KQ + 4 * p;
+    const int p = (lane & 15) ^ (R & 15);
+    dsrc[i] = query_row(A, q0 + R) + 4 * p;
   }
   // fragment read offsets inside a stage buffer: tile nt, k-quarter i -> 16 bytes
   int boff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    boff[i] = row * ROWB + (((HALF ? 8 * (i >> 1) + 2 * kq + (i & 1) : 4 * i + kq) ^ mx2_g(row)) << 4);
+    boff[i] = row * ROWB + (((HALF ? 8 * (i >> 1) + 2 * kq + (i & 1) : 4 * i + kq) ^ row) << 4);
 
   f64x4 sum[NT];
   f32x4 acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    sum[nt] = (f64x4){0.0, 0.0, 0.0, 0.0};      // F64: the accumulator itself
+    sum[nt] = (f64x4){0.0, 0.0, 0.0, 0.0};
     acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
-  const int ng = F / 64;                           // feature groups of 64; stage s = (group s / 6, tap s % 6)
+  const int ng = A.F / 64;                           // feature groups of 64; stage s = (group s / 6, tap s % 6)
   const int nst = NTAPS * ng;
   // The DMA is issued from inline asm so that hipcc's wait-count model does not see it: with an LDS-DMA in the
   // queue the compiler waits vmcnt(0) at the first use of ANY ordinary load, which would drain the candidate
@@ -554,7 +550,7 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
     const int tap = s % NTAPS, e0 = 64 * (s / NTAPS);
 #pragma unroll
     for (int i = 0; i < PIECES / 4; ++i) {
-      const float* gp = dsrc[i] + tap * F + e0;
+      const float* gp = dsrc[i] + tap * A.F + e0;
       const unsigned la = ring_lds + (unsigned)slot * STAGE_BYTES + (w_u + 4 * i) * 1024;
       // m0 is the LDS base of the DMA.  Naming it as a clobber makes hipcc warn that it does not preserve reserved
       // registers across the statement - which matters only if the compiler itself keeps something in m0 around here.
@@ -568,24 +564,21 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
     }
   };
   auto load_a = [&](f32x4 (&a)[4], int s) {
-    const int tap = s % NTAPS, e0 = 64 * (s / NTAPS);
-    const bool ok = at0 + tap * tap_stride < T;
-    if (HALF) {
-      const _Float16* ph = ok ? arow_h + (int64_t)tap * tap_stride * F + e0 : reinterpret_cast<const _Float16*>(zeros);
+    const TapSrc<track_t<HALF>> src = tap_src(A, arow, 0, at0, s % NTAPS, 64 * (s / NTAPS));
+    if constexpr (HALF) {
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
-        const f16x8 h = *reinterpret_cast<const f16x8*>(ph + (ok ? 32 * jj : 0));
+        const f16x8 h = *reinterpret_cast<const f16x8*>(src.p + (src.in_track ? 32 * jj : 0));
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           a[2 * jj][e] = (float)h[e];
           a[2 * jj + 1][e] = (float)h[4 + e];
         }
       }
-      return;
-    }
-    const float* p = ok ? arow + (int64_t)tap * tap_stride * F + e0 : zeros;
+    } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f32x4*>(p + 16 * i);
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f32x4*>(src.p + 16 * i);
+    }
   };
   // candidate fragments: register ring of depth 3 (prefetched two stages = 96 MFMAs ahead: the rows come from HBM);
   // query tile: LDS double buffer, one stage ahead (L2-resident)
@@ -624,11 +617,6 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
         for (int e = 0; e < 4; ++e)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
-            if (F64) {
-              sum[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[2 * half + i][e], (double)b[nt][i][e], sum[nt],
-                                                             0, 0, 0);
-              continue;
-            }
             f32x4 cin = acc[nt];
             if (i == 0 && e == 0) {   // a 32-product chain is complete: into the f64 sum
 #pragma unroll
@@ -653,85 +641,85 @@ __global__ __launch_bounds__(256, QPG_MX2_OCC) void audio_cosine_mx2_kernel(
     for (int sg = 0; sg < 8; ++sg) __builtin_amdgcn_sched_group_barrier(0x008, NT, 0);
     __builtin_amdgcn_sched_barrier(0);
    };
-   stage(MxIC<0>{}); stage(MxIC<1>{}); stage(MxIC<2>{});
+   stage(IC<0>{}); stage(IC<1>{}); stage(IC<2>{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wrapped prefetches
   // C/D layout of v_mfma_f32_16x16x4_f32: lane l, reg r holds (cand row = 4*(l>>4) + r, query col = l&15)
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int q = q0 + nt * 16 + row;
-    if (q >= Q) continue;
-    const double a2 = qn2[q];
+    if (q >= A.Q) continue;
+    const double a2 = A.qn2[q];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      // C/D rows: f32 instruction 4*(l>>4) + r, f64 instruction (l>>4) + 4*r
-      const int64_t cc = c0 + (F64 ? kq + 4 * r : 4 * kq + r);
-      if (cc >= c_end) continue;
-      const double dot = F64 ? sum[nt][r] : sum[nt][r] + (double)acc[nt][r];
-      const double b2 = cn2[cc];
-      const double p = a2 * b2;
-      if (p > 0.0 && p < 1e-32 && stats) atomicOr(&stats[1], 2);
-      const double dd = cosine_from_dot(dot, a2, b2);
-      if (d_f32) reinterpret_cast<float*>(D)[(int64_t)q * ldD + cc] = (float)dd;
-      else D[(int64_t)q * ldD + cc] = dd;
+      const int64_t cc = c0 + (4 * kq + r);
+      if (cc >= A.c_end) continue;
+      const double dot = sum[nt][r] + (double)acc[nt][r];
+      store_pair<false>(A, q, cc, dot, a2);
     }
   }
 }
 
-#define QPG_MX_AD 2      // depth of the candidate-operand register ring
-#define QPG_MX_BD 2      // depth of the query-operand register ring
-#define QPG_MX_KS 4      // contraction slices (waves) per candidate group
-#define QPG_MX_GS 1      // candidate groups per block
-template <int MT, int NT>
-static int launch_audio_mx(qpg_ctx* ctx, void* stream, const float* base, bool half, int N, int T, int F,
-                           const int32_t* cand_t, int G, int tap_stride, const double* cn2, const float* q32,
-                           const double* qn2, int Q, int qtiles_y, double* D, int64_t ldD, int32_t* stats, int64_t c_begin,
-                           int64_t c_end, int d_f32) {
-  constexpr int KS = QPG_MX_KS, GS = QPG_MX_GS;
-  dim3 grid((unsigned)((c_end - c_begin + 16 * MT * GS - 1) / (16 * MT * GS)), (unsigned)qtiles_y);
-  constexpr int AD = QPG_MX_AD;
-  if (half)
-    hipLaunchKernelGGL((audio_cosine_mx_kernel<MT, NT, 6, KS, GS, AD, QPG_MX_BD, true>), grid, dim3(64 * KS * GS), 0,
-                       qpg_stream(stream), base, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD,
-                       (const float*)ctx->zeros, stats, c_begin, c_end, d_f32);
-  else
-    hipLaunchKernelGGL((audio_cosine_mx_kernel<MT, NT, 6, KS, GS, AD, QPG_MX_BD, false>), grid, dim3(64 * KS * GS), 0,
-                       qpg_stream(stream), base, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD,
-                       (const float*)ctx->zeros, stats, c_begin, c_end, d_f32);
-  QPG_LAUNCH_CHECK("audio_cosine_mx_kernel");
-  return QPG_OK;
-}
-
-template <int MT>
-static int launch_audio_mx_q(qpg_ctx* ctx, void* stream, const float* base, bool half, int N, int T, int F,
-                             const int32_t* cand_t, int G, int tap_stride, const double* cn2, const float* q32,
-                             const double* qn2, int Q, double* D, int64_t ldD, int32_t* stats, int64_t c_begin,
-                             int64_t c_end, int d_f32) {
-  const int qt = (Q + 15) / 16;  // widest query tile that divides the work without an empty tail (48 queries = 3)
-#define QPG_MX_ARGS ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q
-  if (qt % 3 == 0) return launch_audio_mx<MT, 3>(QPG_MX_ARGS, qt / 3, D, ldD, stats, c_begin, c_end, d_f32);
-  if (qt % 4 == 0) return launch_audio_mx<MT, 4>(QPG_MX_ARGS, qt / 4, D, ldD, stats, c_begin, c_end, d_f32);
-  if (qt % 2 == 0) return launch_audio_mx<MT, 2>(QPG_MX_ARGS, qt / 2, D, ldD, stats, c_begin, c_end, d_f32);
-  return launch_audio_mx<MT, 1>(QPG_MX_ARGS, qt, D, ldD, stats, c_begin, c_end, d_f32);
-#undef QPG_MX_ARGS
-}
-
-static int audio_cosine_mx(const char* name, qpg_ctx* ctx, void* stream, const float* base, bool half, int N, int T, int F,
-                           const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
-                           const double* qn2, int Q, void* D_, int64_t ldD, int32_t* stats, int d_f32) {
-  double* D = static_cast<double*>(D_);          // (an f32 matrix when d_f32: the kernels cast at the store)
+// ---- host: one set of checks, one argument struct, one choice of instantiation --------------------------------------------
+static int audio_args(AudioArgs* A, const char* name, qpg_ctx* ctx, const void* base, bool half, int N, int T, int F,
+                      const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
+                      const double* qn2, int Q, void* D, int d_f32, int64_t ldD, int32_t* stats) {
+  QPG_REQUIRE(!half || (reinterpret_cast<uintptr_t>(base) % 16) == 0, "%s: base must be 16-byte aligned", name);
   QPG_REQUIRE(ctx && base && cand_t && cn2 && q32 && qn2 && D, "%s: null pointer", name);
   QPG_REQUIRE(N >= 0 && T > 0 && G > 0 && Q >= 0 && tap_stride > 0 && ldD >= (int64_t)N * G, "%s: bad size", name);
-  if (n_taps != 6 || F <= 0 || (F % 128) != 0) {
+  if (n_taps != NTAPS || F <= 0 || (F % 128) != 0) {
     qpg_set_error("%s: compiled for n_taps=6 and F %% 128 == 0 (got n_taps=%d F=%d)", name, n_taps, F);
     return QPG_EUNSUP;
   }
-  if (N == 0 || Q == 0) return QPG_OK;
-  const int64_t C = (int64_t)N * G;
+  *A = AudioArgs{};
+  A->base = base, A->N = N, A->T = T, A->F = F;
+  A->cand_t = cand_t, A->G = G, A->tap_stride = tap_stride, A->cn2 = cn2;
+  A->q32 = q32, A->qn2 = qn2, A->Q = Q;
+  A->D = D, A->d_f32 = d_f32, A->ldD = ldD;
+  A->zeros = ctx->zeros, A->stats = stats;
+  A->c_begin = 0, A->c_end = (int64_t)N * G;      // every candidate; audio_cosine_mx() narrows the range per launch
+  return QPG_OK;
+}
+
+template <typename K>
+static int launch_sweep(K kernel, const char* label, void* stream, dim3 grid, const AudioArgs& A) {
+  hipLaunchKernelGGL(kernel, grid, dim3(64 * KS), 0, qpg_stream(stream), A);
+  QPG_LAUNCH_CHECK(label);
+  return QPG_OK;
+}
+// f(HALF as a constant): the instantiation for an f16 or an f32 track
+template <typename Fn>
+static int for_track(bool half, Fn f) {
+  return half ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(NT as a constant, query tiles along y): the widest query tile that divides the work without an empty tail (48 queries = 3)
+template <typename Fn>
+static int for_query_tile(int Q, Fn f) {
+  const int qt = (Q + 15) / 16;
+  if (qt % 3 == 0) return f(IC<3>{}, qt / 3);
+  if (qt % 4 == 0) return f(IC<4>{}, qt / 4);
+  if (qt % 2 == 0) return f(IC<2>{}, qt / 2);
+  return f(IC<1>{}, qt);
+}
+
+// split-K blocks of MT tiles over the candidates [A.c_begin, A.c_end)
+template <int MT>
+static int launch_audio_mx_q(void* stream, bool half, const AudioArgs& A) {
+  return for_query_tile(A.Q, [&](auto nt, int qtiles_y) {
+    const dim3 grid((unsigned)((A.c_end - A.c_begin + 16 * MT - 1) / (16 * MT)), (unsigned)qtiles_y);
+    return for_track(half, [&](auto h) {
+      return launch_sweep(audio_cosine_mx_kernel<MT, decltype(nt)::value, decltype(h)::value>, "audio_cosine_mx_kernel",
+                          stream, grid, A);
+    });
+  });
+}
+
+static int audio_cosine_mx(const qpg_ctx* ctx, void* stream, bool half, AudioArgs A) {
+  const int64_t C = A.c_end;
   // Work split.  mx2 blocks take 64 candidates x 48 queries; they are all resident at once (5 fit per CU), so the
   // launch is balanced when every CU holds the same number of them: whole multiples of n_cu blocks go to mx2, the
   // remaining candidates to split-K blocks of ONE 16-candidate tile (4 waves share it), which balance to a tile per CU.
-  const int ny = (Q + 47) / 48;
+  const int ny = (A.Q + 47) / 48;
   const int64_t nbx = C / 64;
   int64_t main_x;
   if (ny >= 4) main_x = nbx;
@@ -741,100 +729,69 @@ static int audio_cosine_mx(const char* name, qpg_ctx* ctx, void* stream, const f
   // a short remainder rides in the SAME launch (blocks main_x .. main_x + tail_tiles - 1: split-K, one tile each)
   const bool ride = main_x > 0 && tail_tiles > 0 && tail_tiles <= 4 * (int64_t)ctx->n_cu && ny == 1;
   if (main_x > 0) {
-    dim3 grid((unsigned)(main_x + (ride ? tail_tiles : 0)), (unsigned)ny);
-    if (half)
-      hipLaunchKernelGGL((audio_cosine_mx2_kernel<3, 6, false, true>), grid, dim3(256), 0, qpg_stream(stream), base, N, T,
-                         F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, (const float*)ctx->zeros, stats, (int64_t)0,
-                         c_mid, (int)main_x, C, d_f32);
-    else
-      hipLaunchKernelGGL((audio_cosine_mx2_kernel<3, 6, false, false>), grid, dim3(256), 0, qpg_stream(stream), base, N, T,
-                         F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, (const float*)ctx->zeros, stats, (int64_t)0,
-                         c_mid, (int)main_x, C, d_f32);
-    QPG_LAUNCH_CHECK("audio_cosine_mx2_kernel");
+    A.c_end = c_mid;
+    A.main_blocks = (int)main_x;
+    A.c_tail_end = C;
+    const dim3 grid((unsigned)(main_x + (ride ? tail_tiles : 0)), (unsigned)ny);
+    const int rc = for_track(half, [&](auto h) {
+      return launch_sweep(audio_cosine_mx2_kernel<decltype(h)::value>, "audio_cosine_mx2_kernel", stream, grid, A);
+    });
+    if (rc != QPG_OK) return rc;
   }
   if (c_mid == C || ride) return QPG_OK;
-  if (tail_tiles * ny <= 4 * (int64_t)ctx->n_cu)
-    return launch_audio_mx_q<1>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, stats,
-                                c_mid, C, d_f32);
-  return launch_audio_mx_q<2>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, stats, c_mid,
-                              C, d_f32);
+  A.c_begin = c_mid;
+  A.c_end = C;
+  if (tail_tiles * ny <= 4 * (int64_t)ctx->n_cu) return launch_audio_mx_q<1>(stream, half, A);
+  return launch_audio_mx_q<2>(stream, half, A);
+}
+
+static int audio_cosine(void* stream, bool half, const AudioArgs& A) {
+  return for_query_tile(A.Q, [&](auto nt, int qtiles_y) {
+    const dim3 grid((unsigned)((A.c_end - A.c_begin + 31) / 32), (unsigned)qtiles_y);
+    return for_track(half, [&](auto h) {
+      return launch_sweep(audio_cosine_f64_kernel<decltype(nt)::value, decltype(h)::value>, "audio_cosine_f64_kernel",
+                          stream, grid, A);
+    });
+  });
+}
+
+// the four entry points: mx = the mixed sweep (else the exact one, which writes f64 and has no stats word)
+static int audio_sweep(const char* name, bool mx, bool half, qpg_ctx* ctx, void* stream, const void* base, int N, int T,
+                       int F, const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
+                       const double* qn2, int Q, void* D, int d_f32, int64_t ldD, int32_t* stats) {
+  AudioArgs A;
+  const int rc = audio_args(&A, name, ctx, base, half, N, T, F, cand_t, G, n_taps, tap_stride, cn2, q32, qn2, Q, D, d_f32,
+                            ldD, stats);
+  if (rc != QPG_OK || N == 0 || Q == 0) return rc;
+  return mx ? audio_cosine_mx(ctx, stream, half, A) : audio_cosine(stream, half, A);
 }
 
 extern "C" int qpg_audio_cosine_mx(qpg_ctx* ctx, void* stream, const float* base, int N, int T, int F,
                                    const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2,
                                    const float* q32, const double* qn2, int Q, void* D, int d_is_f32, int64_t ldD,
                                    int32_t* stats) {
-  return audio_cosine_mx("qpg_audio_cosine_mx", ctx, stream, base, false, N, T, F, cand_t, G, n_taps, tap_stride, cn2, q32,
-                         qn2, Q, D, ldD, stats, d_is_f32);
+  return audio_sweep("qpg_audio_cosine_mx", true, false, ctx, stream, base, N, T, F, cand_t, G, n_taps, tap_stride, cn2, q32,
+                     qn2, Q, D, d_is_f32, ldD, stats);
 }
 
 extern "C" int qpg_audio_cosine_mx_h(qpg_ctx* ctx, void* stream, const void* base_f16, int N, int T, int F,
                                      const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2,
                                      const float* q32, const double* qn2, int Q, void* D, int d_is_f32, int64_t ldD,
                                      int32_t* stats) {
-  QPG_REQUIRE((reinterpret_cast<uintptr_t>(base_f16) % 16) == 0, "qpg_audio_cosine_mx_h: base must be 16-byte aligned");
-  return audio_cosine_mx("qpg_audio_cosine_mx_h", ctx, stream, static_cast<const float*>(base_f16), true, N, T, F, cand_t, G,
-                         n_taps, tap_stride, cn2, q32, qn2, Q, D, ldD, stats, d_is_f32);
-}
-
-template <int MT, int NT>
-static int launch_audio(qpg_ctx* ctx, void* stream, const void* base, bool half, int N, int T, int F,
-                        const int32_t* cand_t, int G, int tap_stride, const double* cn2, const float* q32,
-                        const double* qn2, int Q, int qtiles_y, double* D, int64_t ldD, int64_t c_begin, int64_t c_end) {
-  dim3 grid((unsigned)((c_end - c_begin + 16 * MT - 1) / (16 * MT)), (unsigned)qtiles_y);
-  // 4 waves (one per SIMD) split the feature axis.  An 8-wave split (finer work units, 6.5 instead of
-  // 3.25 rounds of blocks at N_db=2048) measured slower on MI355X: 703 vs 629 us (r01 notes).
-  if (half)
-    hipLaunchKernelGGL((audio_cosine_f64_kernel<MT, NT, 6, 4, true>), grid, dim3(256), 0, qpg_stream(stream), base, N, T,
-                       F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, (const float*)ctx->zeros, c_begin, c_end);
-  else
-    hipLaunchKernelGGL((audio_cosine_f64_kernel<MT, NT, 6, 4, false>), grid, dim3(256), 0, qpg_stream(stream), base, N, T,
-                       F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, (const float*)ctx->zeros, c_begin, c_end);
-  QPG_LAUNCH_CHECK("audio_cosine_f64_kernel");
-  return QPG_OK;
-}
-
-template <int MT>
-static int launch_audio_q(qpg_ctx* ctx, void* stream, const void* base, bool half, int N, int T, int F,
-                          const int32_t* cand_t, int G, int tap_stride, const double* cn2, const float* q32,
-                          const double* qn2, int Q, double* D, int64_t ldD, int64_t c_begin, int64_t c_end) {
-  const int qt = (Q + 15) / 16;  // widest query tile that divides the work without an empty tail (48 queries = 3)
-#define QPG_AUDIO_ARGS ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q
-  if (qt % 3 == 0) return launch_audio<MT, 3>(QPG_AUDIO_ARGS, qt / 3, D, ldD, c_begin, c_end);
-  if (qt % 4 == 0) return launch_audio<MT, 4>(QPG_AUDIO_ARGS, qt / 4, D, ldD, c_begin, c_end);
-  if (qt % 2 == 0) return launch_audio<MT, 2>(QPG_AUDIO_ARGS, qt / 2, D, ldD, c_begin, c_end);
-  return launch_audio<MT, 1>(QPG_AUDIO_ARGS, qt, D, ldD, c_begin, c_end);
-#undef QPG_AUDIO_ARGS
-}
-
-// Split-K blocks throughout.  The LDS-shared-query organisation of the mixed sweep (mx2<F64>) for whole rounds of blocks was
-// NOT faster for f64: at 64 cycles per MFMA the split-K kernel is already at the matrix pipe's pace (MI355X: 594 vs 590 us
-// at Q = 48, 0.83 vs 0.81 of the roof at Q = 768, 0.79 vs 0.76 ms per step).
-static int audio_cosine(const char* name, qpg_ctx* ctx, void* stream, const void* base, bool half, int N, int T, int F,
-                        const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2, const float* q32,
-                        const double* qn2, int Q, double* D, int64_t ldD) {
-  QPG_REQUIRE(ctx && base && cand_t && cn2 && q32 && qn2 && D, "%s: null pointer", name);
-  QPG_REQUIRE(N >= 0 && T > 0 && G > 0 && Q >= 0 && tap_stride > 0 && ldD >= (int64_t)N * G, "%s: bad size", name);
-  if (n_taps != 6 || F <= 0 || (F % 128) != 0) {
-    qpg_set_error("%s: compiled for n_taps=6 and F %% 128 == 0 (got n_taps=%d F=%d)", name, n_taps, F);
-    return QPG_EUNSUP;
-  }
-  if (N == 0 || Q == 0) return QPG_OK;
-  const int64_t C = (int64_t)N * G;
-  return launch_audio_q<2>(ctx, stream, base, half, N, T, F, cand_t, G, tap_stride, cn2, q32, qn2, Q, D, ldD, 0, C);
+  return audio_sweep("qpg_audio_cosine_mx_h", true, true, ctx, stream, base_f16, N, T, F, cand_t, G, n_taps, tap_stride, cn2,
+                     q32, qn2, Q, D, d_is_f32, ldD, stats);
 }
 
 extern "C" int qpg_audio_cosine_f64(qpg_ctx* ctx, void* stream, const float* base, int N, int T, int F,
                                     const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2,
                                     const float* q32, const double* qn2, int Q, double* D, int64_t ldD) {
-  return audio_cosine("qpg_audio_cosine_f64", ctx, stream, base, false, N, T, F, cand_t, G, n_taps, tap_stride, cn2, q32,
-                      qn2, Q, D, ldD);
+  return audio_sweep("qpg_audio_cosine_f64", false, false, ctx, stream, base, N, T, F, cand_t, G, n_taps, tap_stride, cn2,
+                     q32, qn2, Q, D, 0, ldD, nullptr);
 }
 
 extern "C" int qpg_audio_cosine_f64_h(qpg_ctx* ctx, void* stream, const void* base_f16, int N, int T, int F,
                                       const int32_t* cand_t, int G, int n_taps, int tap_stride, const double* cn2,
                                       const float* q32, const double* qn2, int Q, double* D, int64_t ldD) {
-  QPG_REQUIRE((reinterpret_cast<uintptr_t>(base_f16) % 16) == 0, "qpg_audio_cosine_f64_h: base must be 16-byte aligned");
-  return audio_cosine("qpg_audio_cosine_f64_h", ctx, stream, base_f16, true, N, T, F, cand_t, G, n_taps, tap_stride, cn2,
-                      q32, qn2, Q, D, ldD);
+  return audio_sweep("qpg_audio_cosine_f64_h", false, true, ctx, stream, base_f16, N, T, F, cand_t, G, n_taps, tap_stride,
+                     cn2, q32, qn2, Q, D, 0, ldD, nullptr);
 }

@@ -142,10 +142,6 @@ __device__ __forceinline__ double cosine_from_dot(double dot, double qn2, double
   return 1.0 - dot / (nq * nc);
 }
 
-// A-priori error bound of the mixed-precision audio sweep (qpg_audio_cosine_mx, derivation in qpg_audio.hip):
-// |D_mx[q][c] - D_f64[q][c]| <= gamma_32 (f32 FMA chains of 32 products) + f64 noise, for every pair.
-// (the value is QPG_AUDIO_MX_ERR of include/qpg.h)
-
 // ---- stable ranks of a table row by sorting (round 3) -----------------------------------------------------------------
 // rank[k] = #{o : v[o] < v[k] or (v[o] == v[k] and o < k)} - what np.argsort(kind='stable') followed by argsort gives
 // (GestureKNN.py:544-556 ranks its distance rows; the unstable-sort contract for exact ties is DESIGN.md §2).  Counting
