@@ -1059,6 +1059,59 @@ int qpg_bert_attention_f32(qpg_ctx*, void* stream, const float* qkv, const int32
 int qpg_bert_mean_pool_f32(qpg_ctx*, void* stream, const float* x, const int32_t* seq_start, int S, int64_t R, int max_len,
                            int D, float* out, int32_t* err);
 
+/* ---- The GRU speech-to-code generator (codebook/generate/generate.py Generator_gru, inference): the stage kernels that
+ * qpgesture_amd/generate.py chains with qpg_wavlm_gemm_f32.  All arrays [dev] f32 unless stated, activations
+ * channels-last rows [B][T][C].  No launch of this section synchronises between blocks. ---- */
+#define QPG_GEN_TAPS 16            /* taps of every convolution of the WavEncoder                          */
+#define QPG_GEN_HIDDEN 200         /* the GRU's hidden width: the only one the recurrence kernel is built for */
+#define QPG_GEN_GRU_BATCH_TILE 16  /* sequences one recurrence block owns                                  */
+#define QPG_GEN_CONV_TIME_TILE 128 /* output frames one convolution block owns (Cin > 1)                   */
+#define QPG_GEN_HEAD_LD 208        /* row stride of qpg_gen_head_ln_f32's output (QPG_GEN_HIDDEN padded to 16) */
+
+/* Output frames of an unpadded 16-tap Conv1d: (t_in - 16) / stride + 1, 0 if t_in < 16. */
+int64_t qpg_gen_conv_frames(int64_t t_in, int stride);
+
+/* Conv1d(Cin, Cout, 16, stride), no padding, with an optional epilogue:
+ *   out[b][t][co] = act(bn(bias[co] + sum_{j < 16, ci < Cin} w[co][j][ci] x[b][stride t + j][ci])),  t < T =
+ *   qpg_gen_conv_frames(Tin, stride)
+ * x [B][Tin][Cin] (Cin == 1: the raw samples [B][Tin]); w [Cout][16][Cin] - torch's [Cout][Cin][16] with the last two
+ * axes swapped; bias [Cout] or NULL; bn [4][Cout] = BatchNorm1d's weight, bias, running_mean, running_var, applied as
+ * (v - mean) / sqrt(var + eps) * weight + bias, or NULL (no BatchNorm); act != 0: LeakyReLU, v < 0 -> slope v; out
+ * [B][T][Cout].  The (Tin - 16) % stride trailing input frames that no output window covers are never read.  Cin == 1 runs
+ * on the VALU (Cout a multiple of 8, <= 64); Cin a multiple of 4 is an implicit GEMM with K = 16 Cin on the f32 matrix
+ * cores (Cout a multiple of 16, <= 64); anything else QPG_EUNSUP, nothing launched.  w, out and, with Cin > 1, x 16-byte aligned. */
+int qpg_gen_conv1d_f32(qpg_ctx*, void* stream, const float* x, int B, int64_t Tin, int Cin, const float* w,
+                       const float* bias, const float* bn, float eps, int act, float slope, int Cout, int stride, float* out);
+
+/* The recurrence of one bidirectional GRU layer (torch.nn.GRU, h0 = 0, gate order r, z, n):
+ *   xp  [B][T][2][3 H]  W_ih x + b_ih of direction 0 | direction 1 (one qpg_wavlm_gemm_f32 with N = 6 H),
+ *   whh [2][3 H][H], bhh [2][3 H],
+ *   out [B][T][2 H]     h_t of direction 0 | direction 1; direction 1 walks t = T - 1 .. 0.
+ *   r = s(xp_r + (W_hr h + b_hr)), z = s(xp_z + (W_hz h + b_hz)), n = tanh(xp_n + r (W_hn h + b_hn)), h' = (1 - z) n + z h.
+ * One block owns QPG_GEN_GRU_BATCH_TILE sequences of one direction for all T steps (h in LDS, W_hh streamed from L2 per
+ * step); a sequence's output bits depend neither on B nor on its position in the batch, and the two directions run the
+ * same instructions.  H != QPG_GEN_HIDDEN: QPG_EUNSUP, nothing launched.  All pointers 16-byte aligned. */
+int qpg_gen_gru_layer_f32(qpg_ctx*, void* stream, const float* xp, const float* whh, const float* bhh, int B, int T, int H,
+                          float* out);
+
+/* The head's first half: y[r][0 .. H) = LayerNorm(x[r][0 .. H) + x[r][H .. 2 H)) gamma + beta (biased variance of the
+ * centred values, eps inside the root), y[r][H .. QPG_GEN_HEAD_LD) = 0.  x [R][2 H] (a GRU layer's output), y
+ * [R][QPG_GEN_HEAD_LD]: the A operand of the head's qpg_wavlm_gemm_f32 against out.weight padded to the same stride.
+ * H != QPG_GEN_HIDDEN: QPG_EUNSUP. */
+int qpg_gen_head_ln_f32(qpg_ctx*, void* stream, const float* x, const float* gamma, const float* beta, int64_t R, int H,
+                        float eps, float* y);
+
+/* codes[r] = argmax_c logits[r][c]: logits [R][N], codes [dev] i64 [R].  ON EXACT TIES THE LOWEST INDEX WINS (a row of
+ * equal values gives 0).  Rows are assumed NaN-free. */
+int qpg_gen_argmax_f32(qpg_ctx*, void* stream, const float* logits, int64_t R, int N, int64_t* codes);
+
+/* loss[0] = mean_r (log sum_c exp(logits[r][c]) - logits[r][target[r]]), F.cross_entropy's default reduction: logits
+ * [R][N], target [dev] i64 [R], loss [dev] f32 [1].  The row terms are f32 (the row maximum subtracted before exp), their
+ * mean is accumulated in f64 in a fixed order.  A target outside [0, N) is not used as an index: its row term, and so the
+ * loss, is NaN.  ws: [dev] f32 scratch of R floats (the row terms); contents on entry are ignored. */
+int qpg_gen_cross_entropy_f32(qpg_ctx*, void* stream, const float* logits, const int64_t* target, int64_t R, int N,
+                              float* ws, float* loss);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

@@ -477,3 +477,53 @@ def make_vocab():
               "中", "文", "0", "1", "2", "##0", "##1"]
     assert len(words) == 97 and len(set(words)) == 97
     return words
+
+
+# ----------------------------------------------------------------------------------------------
+# The GRU speech-to-code generator (codebook/generate/generate.py Generator_gru): seeded weights with the reference's
+# key names
+# ----------------------------------------------------------------------------------------------
+GENERATOR_CONVS = [(1, 8, 3), (8, 16, 3), (16, 32, 6), (32, 64, 6), (64, 32, 6)]      # (Cin, Cout, stride), 16 taps each
+GENERATOR_HIDDEN, GENERATOR_CODES = 200, 512
+
+
+def make_generator_state_dict(seed, prefix="module."):
+    """No end2end checkpoint ships with the reference.  Seeded Generator_gru() weights with the reference's key names and
+    shapes (end2end.py saves a DataParallel state_dict: keys carry `module.`).  Every tensor is drawn uniform within
+    torch's default bound 1 / sqrt(fan_in) times a gain: convolutions x 2, GRU x 3, out.weight x 4 - at torch's own
+    scales a 4 s window yields one or two distinct codes and the recurrence barely matters - and the BatchNorm running
+    statistics and affines are drawn away from (0, 1)."""
+    rng = _rng(seed)
+    H, C = GENERATOR_HIDDEN, GENERATOR_CODES
+    sd = {}
+
+    def f32(a):
+        return np.ascontiguousarray(a, np.float32)
+
+    def uniform(name, shape, fan_in, gain=1.0):
+        b = gain / np.sqrt(fan_in)
+        sd[prefix + name] = f32(rng.uniform(-b, b, shape))
+
+    enc = "WavEncoder.feat_extractor."
+    for i, (cin, cout, _) in enumerate(GENERATOR_CONVS):
+        uniform(enc + "%d.weight" % (3 * i), (cout, cin, 16), cin * 16, 2.0)
+        uniform(enc + "%d.bias" % (3 * i), (cout,), cin * 16)
+        if i < 4:
+            bn = enc + "%d." % (3 * i + 1)
+            sd[prefix + bn + "weight"] = f32(rng.uniform(0.6, 1.4, cout) * rng.choice([-1.0, 1.0], cout))
+            sd[prefix + bn + "bias"] = f32(rng.standard_normal(cout) * 0.1)
+            sd[prefix + bn + "running_mean"] = f32(rng.standard_normal(cout) * 0.05)
+            sd[prefix + bn + "running_var"] = f32(rng.uniform(0.05, 0.2, cout))
+            sd[prefix + bn + "num_batches_tracked"] = np.array(1000, np.int64)
+    for layer, nin in ((0, 32), (1, 2 * H)):
+        for suffix in ("", "_reverse"):
+            tag = "_l%d%s" % (layer, suffix)
+            uniform("project.weight_ih" + tag, (3 * H, nin), H, 3.0)
+            uniform("project.weight_hh" + tag, (3 * H, H), H, 3.0)
+            uniform("project.bias_ih" + tag, (3 * H,), H, 3.0)
+            uniform("project.bias_hh" + tag, (3 * H,), H, 3.0)
+    sd[prefix + "norm.weight"] = f32(rng.uniform(0.6, 1.4, H))
+    sd[prefix + "norm.bias"] = f32(rng.standard_normal(H) * 0.1)
+    uniform("out.weight", (C, H), H, 4.0)
+    uniform("out.bias", (C,), H)
+    return sd
