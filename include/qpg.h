@@ -1112,6 +1112,103 @@ int qpg_gen_argmax_f32(qpg_ctx*, void* stream, const float* logits, int64_t R, i
 int qpg_gen_cross_entropy_f32(qpg_ctx*, void* stream, const float* logits, const int64_t* target, int64_t R, int N,
                               float* ws, float* loss);
 
+/* ---- Training of the same generator (codebook/end2end.py): the stage kernels that qpgesture_amd/end2end.py chains with
+ * qpg_gen_conv1d_f32 (bn = NULL, act = 0: the training forward's convolutions), qpg_wavlm_gemm_f32 (input projections,
+ * head, and every data gradient of a Linear against a transposed weight copy), qpg_gen_head_ln_f32,
+ * qpg_gen_cross_entropy_f32 and qpg_adam_step_f32.  All arrays [dev] f32 unless stated, activations channels-last rows,
+ * weights in the layouts of the section above.  Every sum over rows is two-stage and fixed-order: f32 or f64 partials
+ * per block or slab, added in block / slab order in f64, so two runs from the same state are bit-identical; there are no
+ * global atomics and no launch waits on another block.  Workspaces are caller-owned, their contents on entry are ignored.
+ * Gradients are overwritten, not accumulated. ---- */
+#define QPG_GEN_TRAIN_MAX_SLABS 1024    /* most row slabs a weight gradient is split into                                */
+#define QPG_GEN_TRAIN_SLAB_MIN_ROWS 64  /* no slab is planned smaller than this (a single slab may be)                   */
+#define QPG_GEN_BN_MAX_BLOCKS 1024      /* most partials of a BatchNorm sum; a block takes 1024 / C rows per pass        */
+#define QPG_GEN_GRU_SAVED 4             /* planes the training recurrence saves per (b, t, direction): r, z, n, W_hn h + b_hn */
+
+/* BatchNorm1d in train() mode over [R][C] rows (R = B T_i), C in {8, 16, 32, 64} (else QPG_EUNSUP), R >= 2.
+ * qpg_gen_bn_stats_f32: stat [2][C] = the batch mean and the BIASED variance per channel, both from f64 sums of x and
+ *   x^2 (block b owns the row groups b, b + blocks, .. of 1024 / C rows; blocks = min(groups, QPG_GEN_BN_MAX_BLOCKS)).
+ *   running_mean / running_var (each optional): r = (1 - momentum) r + momentum v with v the mean, resp. the UNBIASED
+ *   variance var R / (R - 1).
+ * qpg_gen_bn_apply_f32: y = leaky((x - mean) / sqrt(var + eps) * gamma + beta), v <= 0 -> slope v.  y may be x.
+ * qpg_gen_bn_backward_f32: with dyh = dy where y > 0, slope dy where y <= 0 (y: the forward's OUTPUT; at exactly 0 the
+ *   slope, as torch does), xhat = (x - mean) / sigma: dbeta = sum dyh, dgamma = sum dyh xhat, dx = (gamma / sigma) (dyh -
+ *   mean(dyh) - xhat mean(dyh xhat)).  x is the forward's input, stat what qpg_gen_bn_stats_f32 wrote.  dx may be dy.
+ * ws: 8-byte aligned, at least qpg_gen_bn_ws_floats(R, C) floats (it holds f64 partials); x, y, dy, dx 16-byte aligned. */
+int64_t qpg_gen_bn_ws_floats(int64_t R, int C);
+int qpg_gen_bn_stats_f32(qpg_ctx*, void* stream, const float* x, int64_t R, int C, float* ws, int64_t ws_floats, float* stat,
+                         float* running_mean, float* running_var, float momentum);
+int qpg_gen_bn_apply_f32(qpg_ctx*, void* stream, const float* x, int64_t R, int C, const float* stat, const float* gamma,
+                         const float* beta, float eps, float slope, float* y);
+int qpg_gen_bn_backward_f32(qpg_ctx*, void* stream, const float* x, const float* y, const float* dy, int64_t R, int C,
+                            const float* stat, const float* gamma, float eps, float slope, float* ws, int64_t ws_floats,
+                            float* dgamma, float* dbeta, float* dx);
+
+/* Data gradient of qpg_gen_conv1d_f32's convolution, a gather:
+ *   dx[b][s][ci] = sum over t with 0 <= s - stride t < 16, t < T, and co of dy[b][t][co] w[co][s - stride t][ci]
+ * dy [B][T][Cout], T = qpg_gen_conv_frames(Tin, stride), w the forward's [Cout][16][Cin], dx [B][Tin][Cin].  EVERY frame
+ * of dx is written: the (Tin - 16) % stride trailing frames that no window covers get exactly 0.  Cin in {8, 16, 32, 64},
+ * Cout a multiple of 16 up to 64, stride 3 or 6; anything else QPG_EUNSUP.  dy, w, dx 16-byte aligned. */
+int qpg_gen_conv1d_bwd_data_f32(qpg_ctx*, void* stream, const float* dy, int B, int64_t Tin, int Cin, const float* w,
+                                int Cout, int stride, float* dx);
+
+/* Weight and bias gradient of the same convolution: dw [Cout][16][Cin] (the forward's layout), db [Cout] from the layer
+ * input x [B][Tin][Cin] and dy [B][T][Cout] (16-byte aligned).  Cin == 1 runs on the VALU (a thread owns every 256th row
+ * of a slab and all 8 x 16 sums of a channel group, the block's threads are added in f64 in thread order);
+ * Cin a multiple of 4 is an implicit GEMM on the f32 matrix cores with the contraction over the (b, t) rows of 16 Cin
+ * contiguous floats, as the forward reads them; db is the product with a column of ones.  The B T rows are split into
+ * slabs - as many as ws holds (ws_floats / (Cout 16 Cin + Cout)), at most QPG_GEN_TRAIN_MAX_SLABS, none under
+ * QPG_GEN_TRAIN_SLAB_MIN_ROWS rows - whose partials are added in slab order in f64.  The uncovered trailing input
+ * frames are never read.  Shapes as qpg_gen_conv1d_f32, else QPG_EUNSUP. */
+int64_t qpg_gen_conv1d_wgrad_ws_floats(int Cin, int Cout, int slabs);
+int qpg_gen_conv1d_bwd_weight_f32(qpg_ctx*, void* stream, const float* x, int B, int64_t Tin, int Cin, const float* dy,
+                                  int Cout, int stride, float* dw, float* db, float* ws, int64_t ws_floats);
+
+/* Weight gradient of a Linear, the same matrix-core kernel over plain rows:
+ *   dW[n][k] = sum_r dY[r][n] X[r + shift][k],  db[n] = sum_r dY[r][n]   (db optional),  n < N, k < K
+ * dY rows of ldy, X rows of ldx floats, dW [N][K] contiguous.  shift in {-1, 0, 1} with the period T: row r = (b, t), t =
+ * r % T, pairs with X's row (b, t + shift), and with a ZERO row when t + shift leaves [0, T) - the recurrence's W_hh
+ * gradient pairs dgh of step t with h of the previous step of its direction and never reaches across a batch member; db
+ * takes every row regardless.  With shift == 0, T is ignored.  Slabs and ws as above with qpg_gen_rowgrad_ws_floats(N,
+ * K, slabs).  N, K <= 4096. */
+int64_t qpg_gen_rowgrad_ws_floats(int N, int K, int slabs);
+int qpg_gen_rowgrad_f32(qpg_ctx*, void* stream, const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t R, int N,
+                        int K, int shift, int64_t T, float* dW, float* db, float* ws, int64_t ws_floats);
+
+/* qpg_gen_gru_layer_f32 for training: the same recurrence, instruction for instruction (out is bit-equal), that also
+ * leaves saved [B][T][2][QPG_GEN_GRU_SAVED][H] = r, z, n and W_hn h + b_hn per (b, t, direction, unit). */
+int qpg_gen_gru_layer_train_f32(qpg_ctx*, void* stream, const float* xp, const float* whh, const float* bhh, int B, int T,
+                                int H, float* out, float* saved);
+
+/* Backpropagation through time of one bidirectional layer.  dout [B][T][2 H] the gradient at the layer's output, saved
+ * and out what qpg_gen_gru_layer_train_f32 left, whhT [2][H][3 H] the transposed W_hh per direction;
+ *   dxp [B][T][2][3 H]  the gradient at the input projection xp (gates r, z, n),
+ *   dgh [B][T][2][3 H]  the gradient at W_hh h + b_hh (it differs from dxp in the n gate: times r).
+ * The forward's ownership: one block owns QPG_GEN_GRU_BATCH_TILE sequences of one direction and walks its steps in
+ * reverse; a lane keeps dh of its 4 units of one sequence in registers, the step's dgh goes through LDS into the
+ * product W_hh^T dgh on the matrix cores (a column is one sequence, so a sequence's bits depend neither on B nor on its
+ * position).  The weight gradients are NOT accumulated here: they are qpg_gen_rowgrad_f32 over dxp (W_ih, b_ih) and
+ * over dgh with shift -1 / +1 (W_hh, b_hh of direction 0 / 1).  H != QPG_GEN_HIDDEN: QPG_EUNSUP.  All pointers 16-byte
+ * aligned. */
+int qpg_gen_gru_layer_backward_f32(qpg_ctx*, void* stream, const float* dout, const float* saved, const float* out,
+                                   const float* whhT, int B, int T, int H, float* dxp, float* dgh);
+
+/* Backward of qpg_gen_head_ln_f32: dy [R][QPG_GEN_HEAD_LD] (columns >= H ignored), x [R][2 H] the forward's input; dx
+ * [R][2 H] gets the LayerNorm's input gradient in BOTH halves (the direction sum), dgamma [H] and dbeta [H] - which must
+ * be dgamma + H - the row sums of dy xhat and dy (slab partials from f64 accumulators, added in f64).  ws: at least
+ * qpg_gen_head_ln_bwd_ws_floats(R) floats for full parallelism, 2 H at the least. */
+int64_t qpg_gen_head_ln_bwd_ws_floats(int64_t R);
+int qpg_gen_head_ln_backward_f32(qpg_ctx*, void* stream, const float* dy, const float* x, const float* gamma, int64_t R,
+                                 int H, float eps, float* ws, int64_t ws_floats, float* dgamma, float* dbeta, float* dx);
+
+/* Backward of qpg_gen_cross_entropy_f32: dlogits[r][c] = (softmax(logits[r])[c] - (c == target[r])) / R. */
+int qpg_gen_cross_entropy_backward_f32(qpg_ctx*, void* stream, const float* logits, const int64_t* target, int64_t R, int N,
+                                       float* dlogits);
+
+/* Inverted dropout on a given mask: y[e] = mask[e] ? x[e] * scale : 0, mask [dev] uint8 [n], scale = 1 / (1 - p).  The
+ * backward is the same call on the gradient.  y may be x. */
+int qpg_gen_dropout_f32(qpg_ctx*, void* stream, const float* x, const uint8_t* mask, int64_t n, float scale, float* y);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

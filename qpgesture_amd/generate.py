@@ -1,6 +1,6 @@
 """The GRU speech-to-code generator on the GPU: the reference's baseline WITHOUT motion matching, codebook/inference.py's
 wav -> Generator_gru.sample -> 30 codes per 4 s window -> VQVAE.decode -> poses (the model: codebook/generate/generate.py
-:9-31 WavEncoder, :312-350 Generator_gru).  Inference only: the end2end.py trainer is out of scope.
+:9-31 WavEncoder, :312-350 Generator_gru).  Inference only; the trainer that writes the checkpoint is qpgesture_amd/end2end.py.
 
     from qpgesture_amd.generate import load_generator, cut_windows
     model = load_generator("end2end_checkpoint_080.bin", device="cuda:0")
