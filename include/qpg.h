@@ -1209,6 +1209,38 @@ int qpg_gen_cross_entropy_backward_f32(qpg_ctx*, void* stream, const float* logi
  * backward is the same call on the gradient.  y may be x. */
 int qpg_gen_dropout_f32(qpg_ctx*, void* stream, const float* x, const uint8_t* mask, int64_t n, float scale, float* y);
 
+/* ---- vq-wav2vec code extraction (fairseq's Wav2VecModel.feature_extractor and GumbelVectorQuantizer.forward_idx in eval
+ * mode): what qpgesture_amd/wavvq.py chains with qpg_wavlm_conv0_f32 (layer 0) and qpg_wavlm_gemm_f32 (every later
+ * convolution, lda = stride C, K = taps C, n_outer = B; both Linears of the quantiser).  All arrays [dev] f32 unless
+ * stated, activations channels-last rows [B][T][C]. ---- */
+#define QPG_WAVVQ_GN_SLAB 4096     /* floats of a window one block of the GroupNorm's passes owns */
+#define QPG_WAVVQ_EPI_NONE 0       /* qpg_wavvq_groupnorm_f32's epilogue: none                    */
+#define QPG_WAVVQ_EPI_RELU 1       /*   max(v, 0)                                                 */
+#define QPG_WAVVQ_EPI_RELU_LOG 2   /*   log(|max(v, 0)| + 1): the feature extractor's last layer  */
+
+/* GroupNorm(1, C) per window, in place: with mean and the BIASED variance over all T C values of window b,
+ *   x[b][t][c] = epilogue((x[b][t][c] - mean_b) / sqrt(var_b + eps) * gamma[c] + beta[c])
+ * gamma, beta [C] or NULL (1, resp. 0: a non-affine norm).  Three launches over slabs of QPG_WAVVQ_GN_SLAB consecutive
+ * floats of a window: f64 (sum, sum of squares) per slab into ws, the slabs of a window added in slab order in f64 (mean
+ * and variance from the f64 sums, so a mean far above the standard deviation does not cancel the variance; a constant
+ * window has variance 0 and comes out as beta), then the apply pass.  The activations are read twice and written once.
+ * A window's result depends neither on B nor on its position in the batch; no atomics.  C must be a multiple of 4
+ * (QPG_EUNSUP otherwise, nothing launched); x, gamma, beta 16-byte aligned.
+ * ws: 8-byte aligned, at least qpg_wavvq_groupnorm_ws_floats(B, T, C) floats (QPG_EINVAL below that, nothing launched);
+ * contents on entry are ignored. */
+int64_t qpg_wavvq_groupnorm_ws_floats(int B, int64_t T, int C);
+int qpg_wavvq_groupnorm_f32(qpg_ctx*, void* stream, float* x, int B, int64_t T, int C, const float* gamma,
+                            const float* beta, float eps, int epilogue, float* ws, int64_t ws_floats);
+
+/* x[e] = max(x[e], 0) for e < n, in place: the ReLU between the two Linears of the quantiser's weight_proj (their biases
+ * are the GEMM's).  n a multiple of 4 (QPG_EUNSUP otherwise), x 16-byte aligned. */
+int qpg_wavvq_relu_f32(qpg_ctx*, void* stream, float* x, int64_t n);
+
+/* codes[r][g] = argmax_v logits[r][g][v]: logits [R][G][V], codes [dev] i64 [R][G] - forward_idx's indices.  ON EXACT TIES
+ * THE LOWEST INDEX WINS, as torch.max does (a group of equal values gives 0).  It is qpg_gen_argmax_f32 over the
+ * [R G][V] view of the logits.  Rows are assumed NaN-free. */
+int qpg_wavvq_group_argmax_f32(qpg_ctx*, void* stream, const float* logits, int64_t R, int G, int V, int64_t* codes);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

@@ -10,10 +10,11 @@ Reads  <save_dir>/<prefix>/<prefix>_<split>_240.npz['body'] (N,240,135) for spli
 writes <save_dir>/<prefix>/<prefix>_<split>_240_code.npz['code'] int64 (N,30) — the files GestureKNN.py takes
 as --train_codebook.  With --WavLM_model_path ({'cfg', 'model'} checkpoint) it also reads the same files' ['wav']
 (N,64000) and writes <prefix>_<split>_240_WavLM.npz['wavlm'] f32 (N,199,D), the --train_wavlm files, through the HIP
-WavLM of qpgesture_amd/wavlm.py; without the flag nothing else changes.  Same flags as codebook/configs/parse_args.py.
+WavLM of qpgesture_amd/wavlm.py; with --WavVQ_model_path (a vq-wav2vec checkpoint, qpgesture_amd/wavvq.py) it writes
+<prefix>_<split>_240_WavVQ.npz['wavvq'] int64 (N,398,2), the --train_wavvq files (wav_to_vq of the reference, :388-429);
+without the flags nothing else changes.  Same flags as codebook/configs/parse_args.py.
 The sentence embeddings of step 4 (make_txt_dataset's `context` column) are qpgesture_amd/sentence.py (txt_to_context,
-`python -m qpgesture_amd.sentence`); steps 1 and 2 (BVH cutting) and step 4's vq-wav2vec are out of scope (SURVEY.md §2
-row 22).
+`python -m qpgesture_amd.sentence`); steps 1 and 2 (BVH cutting) are out of scope.
 
 The reference encodes one window per call in a Python loop (:314-316); windows are independent, so they are
 encoded in batches of 256 on the GPU (qpg_vq_encode_f32)."""
@@ -38,6 +39,7 @@ def build_parser():
     p.add_argument('--stage', type=str, default="train")
     p.add_argument('--batch', type=int, default=256)       # additive
     p.add_argument('--WavLM_model_path', type=str, required=False)     # additive: also run wav_to_wavlm
+    p.add_argument('--WavVQ_model_path', type=str, required=False)     # additive: also run wav_to_vq
     return p
 
 
@@ -70,13 +72,16 @@ def main(argv=None):
     from .checkpoint import load_config
     args = build_parser().parse_args(argv)
     if args.step != "3":
-        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm) is implemented; steps 1/2 (BVH cutting) and step 4's "
-                         "vq-wav2vec are out of scope, step 4's sentence embeddings are `python -m qpgesture_amd.sentence`")
+        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm, wav_to_vq) is implemented; steps 1/2 (BVH cutting) are "
+                         "out of scope, step 4's sentence embeddings are `python -m qpgesture_amd.sentence`")
     written = dataset_to_code(args.save_dir, args.prefix, 240, args.VQVAE_model_path, load_config(args.config),
                               gpu=args.gpu, batch=args.batch)
     if args.WavLM_model_path:
         from .wavlm import wav_to_wavlm
         wav_to_wavlm(args.save_dir, args.prefix, args.WavLM_model_path, gpu=args.gpu)
+    if args.WavVQ_model_path:
+        from .wavvq import wav_to_vq
+        wav_to_vq(args.save_dir, args.prefix, args.WavVQ_model_path, gpu=args.gpu)
     return written
 
 

@@ -527,3 +527,58 @@ def make_generator_state_dict(seed, prefix="module."):
     uniform("out.weight", (C, H), H, 4.0)
     uniform("out.bias", (C,), H)
     return sd
+
+
+# ----------------------------------------------------------------------------------------------
+# vq-wav2vec (fairseq's Wav2VecModel with a GumbelVectorQuantizer): seeded weights with the checkpoint's key names
+# ----------------------------------------------------------------------------------------------
+WAVVQ_LAYERS = [(10, 5), (8, 4), (4, 2), (4, 2), (4, 2), (1, 1), (1, 1), (1, 1)]      # (kernel, stride) of vq-wav2vec.pt
+
+
+def _wavvq_geom(width, hidden, groups, variables):
+    return dict(conv_feature_layers=str([(width, k, s) for k, s in WAVVQ_LAYERS]), activation="relu",
+                skip_connections_feat=False, log_compression=True, non_affine_group_norm=False, vq_type="gumbel",
+                vq_groups=groups, vq_vars=variables, vq_depth=2, vq_hidden=hidden)
+
+
+WAVVQ_TINY = _wavvq_geom(16, 32, 2, 20)          # the real kernel / stride list at the narrowest width the GEMM takes
+WAVVQ_GUMBEL = _wavvq_geom(512, 1024, 2, 320)    # vq-wav2vec.pt (Gumbel): 64 000 samples -> 398 frames x 2 codes
+
+
+def make_wavvq_state_dict(seed, geom=None):
+    """No vq-wav2vec checkpoint ships with the reference.  Seeded weights with the key names and shapes of fairseq's
+    Wav2VecModel.state_dict() for `geom` (a dict of the checkpoint's args, default WAVVQ_TINY; `vq_hidden` - not a fairseq
+    arg, the loader reads the width off the weights - is the quantiser's hidden width, 2 C in the real model).  The
+    GroupNorm weights are drawn away from 1 (some negative) and its biases away from 0; the second Linear's gain spreads
+    the logits so that the top-2 margins stand clear of f32 rounding.  The keys the extraction ignores
+    (vector_quantizer.vars, feature_aggregator.*, wav2vec_predictions.*) are present, one of each."""
+    from .wavlm import conv_layers_of
+    geom = dict(WAVVQ_TINY if geom is None else geom)
+    rng = _rng(seed)
+    sd = {}
+
+    def f32(a):
+        return np.ascontiguousarray(a, np.float32)
+
+    cin = 1
+    for i, (c, k, s) in enumerate(conv_layers_of(geom)):
+        pre = "feature_extractor.conv_layers.%d." % i
+        sd[pre + "0.weight"] = f32(rng.standard_normal((c, cin, k)) * 1.4 / np.sqrt(cin * k))
+        if not geom.get("non_affine_group_norm", False):
+            sd[pre + "2.weight"] = f32(rng.uniform(0.6, 1.4, c) * rng.choice([-1.0, 1.0], c, p=[0.25, 0.75]))
+            sd[pre + "2.bias"] = f32(rng.standard_normal(c) * 0.1 + 0.2)
+        cin = c
+    G, V, H = geom["vq_groups"], geom["vq_vars"], geom.get("vq_hidden", 2 * cin)
+    wp = "vector_quantizer.weight_proj."
+    if geom.get("vq_depth", 1) == 1:
+        sd[wp + "weight"] = f32(rng.standard_normal((G * V, cin)) * 3.0 / np.sqrt(cin))
+        sd[wp + "bias"] = f32(rng.standard_normal(G * V) * 0.1)
+    else:
+        sd[wp + "0.0.weight"] = f32(rng.standard_normal((H, cin)) * 1.4 / np.sqrt(cin))
+        sd[wp + "0.0.bias"] = f32(rng.standard_normal(H) * 0.1)
+        sd[wp + "1.weight"] = f32(rng.standard_normal((G * V, H)) * 3.0 / np.sqrt(H))
+        sd[wp + "1.bias"] = f32(rng.standard_normal(G * V) * 0.1)
+    sd["vector_quantizer.vars"] = f32(rng.standard_normal((1, G * V, 4)))
+    sd["feature_aggregator.conv_layers.0.0.weight"] = f32(rng.standard_normal((4, 4, 2)))
+    sd["wav2vec_predictions.project_to_steps.bias"] = f32(rng.standard_normal(4))
+    return sd
