@@ -1241,6 +1241,58 @@ int qpg_wavvq_relu_f32(qpg_ctx*, void* stream, float* x, int64_t n);
  * [R G][V] view of the logits.  Rows are assumed NaN-free. */
 int qpg_wavvq_group_argmax_f32(qpg_ctx*, void* stream, const float* logits, int64_t R, int G, int V, int64_t* codes);
 
+/* ---- BVH ingestion (process/beat_data_to_lmdb.py:21-88 process_bvh(modetype='rotation'); qpgesture_amd/process_bvh.py):
+ * motion text -> channel table -> the `upper` rotation features, and the data_mean / data_std column statistics.  All f64,
+ * no atomics, every sum in a fixed order. ---- */
+#define QPG_BVH_BLOCK_BYTES 4096        /* bytes of text one block of the parse kernels owns                          */
+#define QPG_BVH_MAX_TOKEN 1024          /* a longer run of non-whitespace bytes counts as a byte that fits no token   */
+#define QPG_BVH_INFO_TOKENS 0           /* info[]: tokens in the whole text                                           */
+#define QPG_BVH_INFO_FALLBACK 1         /*         fallback tokens among the first n_values (may exceed fb_cap)       */
+#define QPG_BVH_INFO_STATUS 2           /*         OR of the QPG_BVH_ST_* bits, 0 = the values are complete           */
+#define QPG_BVH_ST_BADBYTE 1            /* one of the first n_values tokens does not fit the grammar                  */
+#define QPG_BVH_ST_SHORT 2              /* the text holds fewer than n_values tokens                                  */
+#define QPG_BVH_ST_OVERFLOW 4           /* more fallback tokens than fb_cap: fb_list holds the first fb_cap only      */
+#define QPG_BVH_PLACEHOLDER_BITS 0x7ff8000000627668      /* value slot of a fallback or bad token: a quiet NaN ("bvh") */
+
+/* The motion block of a BVH file (the bytes after the `Frame Time:` line), parsed on the device.
+ *   text     [dev] u8 [n_bytes], 16-byte aligned.  Whitespace is space, tab, CR, LF; a token starts at a non-whitespace byte
+ *            that follows whitespace or the start of the text and runs to the next whitespace byte or the end.  Newlines
+ *            carry no meaning: like pymo, the first n_values tokens are the values in sequence, the rest is ignored (it is
+ *            counted, not parsed).  No byte at or past n_bytes is read.
+ *   values   [dev] f64 [n_values]: values[t] = token t, for t < min(n_values, info[TOKENS]); later slots are not written.
+ *            Grammar  [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?.  A token whose significant digits are an
+ *            integer m <= 2^53 (at most 19 digits read) and whose net decimal exponent k is in [-22, 22] is m * 10^k or
+ *            m / 10^k: one correctly rounded operation on exact operands, the value strtod and Python's float() return;
+ *            the sign is applied by negation ("-0.000000" is -0.0).  Every other well-formed token is a FALLBACK token:
+ *            its slot holds QPG_BVH_PLACEHOLDER_BITS and it is listed for the host to parse.
+ *   fb_list  [dev] i64 [fb_cap][2]: (token index, byte offset of its first byte) of the fallback tokens, in token order;
+ *            rows info[FALLBACK] .. fb_cap - 1 are not written.
+ *   info     [dev] i64 [3], see QPG_BVH_INFO_*; every entry is written by every call.
+ *   ws       [dev] 8-byte aligned, at least qpg_bvh_parse_ws_bytes(n_bytes) bytes; contents on entry are ignored.
+ * Five launches: token starts per block, a scan of the block counts, one thread per token start parses its token, a scan of
+ * the blocks' fallback counts (it also writes info), the blocks with fallback tokens list them. */
+int64_t qpg_bvh_parse_ws_bytes(int64_t n_bytes);
+int qpg_bvh_parse_motion_f64(qpg_ctx*, void* stream, const uint8_t* text, int64_t n_bytes, int64_t n_values, double* values,
+                             int64_t* fb_list, int fb_cap, int64_t* info, void* ws, int64_t ws_bytes);
+
+/* Channel table -> rotation features, one launch.  values [dev] f64 [F][C]; output frame t < T reads input row t * rate
+ * ((T - 1) * rate < F).  col, mirror_col [dev] i32 [J][3] (entries in [0, C): the caller's invariant), mirror_sign [dev] f64
+ * [J][3].  The three angles of joint j are values[row][col[j][0..2]], in degrees, used as scipy's intrinsic 'ZXY' whatever
+ * channels the file names (beat_data_to_lmdb.py:80-85 does the same): R = Rz(a0) Rx(a1) Ry(a2), row-major, into
+ * upper [dev] f64 [T][9 J].  upper_mirror (optional, with both mirror tables): the same from
+ * mirror_sign[j][k] * values[row][mirror_col[j][k]]. */
+int qpg_bvh_rotation_f64(qpg_ctx*, void* stream, const double* values, int64_t F, int C, int rate, int64_t T, int J,
+                         const int32_t* col, const int32_t* mirror_col, const double* mirror_sign, double* upper,
+                         double* upper_mirror);
+
+/* mean [dev] f64 [D] and population standard deviation stdv [dev] f64 [D] (np.std, ddof 0) of the columns of x [dev] f64
+ * [N][D], N >= 1.  Two passes (the mean, then the squared deviations from it), each a two-stage sum in a fixed order.  A
+ * column whose minimum equals its maximum gets that value as its mean and a std of exactly 0.
+ * ws: at least qpg_column_stats_ws_doubles(N, D) doubles; contents on entry are ignored. */
+int64_t qpg_column_stats_ws_doubles(int64_t N, int D);
+int qpg_column_stats_f64(qpg_ctx*, void* stream, const double* x, int64_t N, int D, double* mean, double* stdv, double* ws,
+                         int64_t ws_doubles);
+
 /* ------------------------------------------------------------------------------------------
  * NOT part of the product library: measurement hooks of the kernel experiments.  They are compiled (and exported) only
  * with -DQPG_DEBUG_HOOKS (tools/build_variant.sh <source> <name> "-DQPG_DEBUG_HOOKS": a variant library the tools load

@@ -14,7 +14,10 @@ WavLM of qpgesture_amd/wavlm.py; with --WavVQ_model_path (a vq-wav2vec checkpoin
 <prefix>_<split>_240_WavVQ.npz['wavvq'] int64 (N,398,2), the --train_wavvq files (wav_to_vq of the reference, :388-429);
 without the flags nothing else changes.  Same flags as codebook/configs/parse_args.py.
 The sentence embeddings of step 4 (make_txt_dataset's `context` column) are qpgesture_amd/sentence.py (txt_to_context,
-`python -m qpgesture_amd.sentence`); steps 1 and 2 (BVH cutting) are out of scope.
+`python -m qpgesture_amd.sentence`).  `--step 2` is the motion half of the reference's step 2:
+<save_dir>/Motion/*.bvh of the speaker -> <prefix>/Rotation/*.npz and Rotation_20fps/*.npz, then the windowed
+<prefix>_<split>_240.npz files where <prefix>/Wav exists (qpgesture_amd/process_bvh.py); step 1 (file copying) and the
+audio, MFCC and transcript halves of step 2 are out of scope.
 
 The reference encodes one window per call in a Python loop (:314-316); windows are independent, so they are
 encoded in batches of 256 on the GPU (qpg_vq_encode_f32)."""
@@ -71,9 +74,13 @@ def dataset_to_code(save_dir, prefix, n_frames=240, model_path=None, config=None
 def main(argv=None):
     from .checkpoint import load_config
     args = build_parser().parse_args(argv)
+    if args.step == "2":
+        from .process_bvh import process_speaker
+        return process_speaker(args.save_dir, args.prefix, gpu=args.gpu)
     if args.step != "3":
-        raise SystemExit("only --step 3 (dataset_to_code, wav_to_wavlm, wav_to_vq) is implemented; steps 1/2 (BVH cutting) are "
-                         "out of scope, step 4's sentence embeddings are `python -m qpgesture_amd.sentence`")
+        raise SystemExit("only --step 2 (BVH -> Rotation/, make_dataset: qpgesture_amd/process_bvh.py) and --step 3 "
+                         "(dataset_to_code, wav_to_wavlm, wav_to_vq) are implemented; step 1 (file copying) is out of scope, "
+                         "step 4's sentence embeddings are `python -m qpgesture_amd.sentence`")
     written = dataset_to_code(args.save_dir, args.prefix, 240, args.VQVAE_model_path, load_config(args.config),
                               gpu=args.gpu, batch=args.batch)
     if args.WavLM_model_path:
